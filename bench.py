@@ -8,14 +8,21 @@ BASELINE.json); the same step in bf16 (bf16 MFMA, f32 accumulate) is a labelled 
 throughput (crops/s summed over ranks; each rank runs its own independent batch: the inference
 path shards by crop with no collective -> weak scaling).
 
-Extra fields: the training step (configs[2]/[3]: bs=32 per GPU, hist-weighted BCE + mask loss,
-backward, Adam; DDP over RCCL when N > 1), the dominant kernel's roofline (HIP events around its
-launches over a timed pass), and the CPU baseline (the oracle restatement on the host cores,
-rank 0, N = 1, bounded sample).
+A plain run does only that: set-up, W warm-up steps, the K timed steps, the result line (the extra
+fields below are null).  ``--dump-outputs DIR`` also writes what the last timed step returned to
+its caller (mask / code logits, counts, xy, xyz) as DIR/<name>.npy: same arguments, same inputs, so
+two builds can be compared output for output.
 
-Also the configs[4] leg (rank 0, N = 1): R50 fp16 batched multi-object inference + decode + PnP.
+Extra fields, with ``--full`` only: the training step (configs[2]/[3]: bs=32 per GPU, hist-weighted
+BCE + mask loss, backward, Adam; DDP over RCCL when N > 1), the dominant kernel's roofline (HIP
+events around its launches over a timed pass), the bf16 / bs=1 / PnP / crop / v3 legs, and the CPU
+baseline (the oracle restatement on the host cores, rank 0, N = 1, bounded sample).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-train] [--no-cpu] [--no-multi]
+Also with ``--full``, the configs[4] leg (rank 0, N = 1): R50 fp16 batched multi-object inference +
+decode + PnP.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--no-train] [--no-cpu] [--no-multi]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 ``--gpus N`` (N > 1) without a torchrun environment launches the N ranks itself (one process per
@@ -74,6 +81,11 @@ def parse(argv=None):
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--precision", default="fp32", choices=["bf16", "fp32"],
                     help="headline precision; fp32 = the reference's own arithmetic (bf16 runs as a labelled leg)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every extra leg (roofline, train, bf16, bs=1, PnP, crop, v3, multi-object, CPU "
+                         "baseline); the --no-* switches below choose among them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--no-train", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--train-steps", type=int, default=None)
@@ -118,6 +130,35 @@ def synthetic_lut(seed=0):
     lut = rng.standard_normal((65536, 3)) * 50.0
     lut[::97] = np.nan
     return lut
+
+
+DUMP_BUDGET = 60 * 2 ** 20  # bytes over all dumped arrays (under 64 MB)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: array} -> DIR/<name>.npy, float32.  Over DUMP_BUDGET in all, every
+    array is cut to the same fraction of its (flattened) elements, at indices drawn from a fixed
+    seed: the same elements in every run of the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for i, (name, a) in enumerate(arrays.items()):
+        if total > DUMP_BUDGET:
+            keep = max(1, int(a.size * DUMP_BUDGET / total))
+            idx = np.sort(np.random.default_rng(1000 + i).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def step_arrays(mask, code, counts, xy, xyz):
+    """The step's five outputs on the host.  The decode fills xy / xyz of crop b up to counts[b]
+    only (the rest of the buffers is never written): those rows are zeroed here."""
+    n = counts.cpu().numpy()
+    xy, xyz = xy.cpu().numpy().copy(), xyz.cpu().numpy().copy()
+    for b in range(len(n)):
+        xy[b, n[b]:] = 0
+        xyz[b, n[b]:] = 0
+    return {"mask": mask.cpu().numpy(), "code": code.cpu().numpy(), "counts": n, "xy": xy, "xyz": xyz}
 
 
 def kernel_name(dt, cout, cin_l):
@@ -383,6 +424,8 @@ def dry_run(args, world, rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"stub": a.numpy()})
         print(json.dumps({"metric": "dry-run stub steps/s", "value": round(world * args.steps / el, 2),
                           "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": round(el / args.steps * 1e3, 3), "higher_is_better": True,
@@ -483,7 +526,7 @@ def time_infer(net, x, dec, bboxes, steps, warmup, world, dev, rank, use_graph=T
     def eager_step():
         with torch.no_grad():
             m, c = net(x)
-            return dec(m, c, bboxes, bbox_size=S // 2)
+            return (m, c) + tuple(dec(m, c, bboxes, bbox_size=S // 2))
 
     graph = None
     if use_graph:
@@ -499,7 +542,7 @@ def time_infer(net, x, dec, bboxes, steps, warmup, world, dev, rank, use_graph=T
     def step():
         if graph is None:
             return eager_step()
-        return graph(x)[2:]
+        return graph(x)
 
     for _ in range(warmup):
         step()
@@ -517,9 +560,10 @@ def time_infer(net, x, dec, bboxes, steps, warmup, world, dev, rank, use_graph=T
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
-    n_corr = int(out[0].sum().item())
+    n_corr = int(out[2].sum().item())
+    out = tuple(t.clone() for t in out)  # (mask, code, counts, xy, xyz) of the last timed step
     res = {"el": el, "ms_per_step": el / steps * 1e3, "value": world * B * steps / el, "n_corr": n_corr,
-           "launch": "eager" if graph is None else "hipgraph", "out": tuple(t.clone() for t in out)}
+           "launch": "eager" if graph is None else "hipgraph", "out": out[2:], "step_out": out}
     del graph
     return res
 
@@ -595,7 +639,7 @@ def run(args):
     if world > 1:
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
         world = dist.get_world_size()  # the ranks that actually joined the RCCL group
-    elif not args.no_rccl and not args.no_train:
+    elif args.full and not args.no_rccl and not args.no_train:
         # N = 1: a world-size-1 RCCL group, so the train leg's data-parallel gradient exchange
         # (configs[3]'s code path: GradBuckets' async all_reduce on the RCCL stream) runs for real
         dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{_free_port()}", rank=0, world_size=1,
@@ -623,7 +667,13 @@ def run(args):
     # ------------------------------------------------------------------ inference (value)
     main = time_infer(net, x, dec, bboxes, args.steps, args.warmup, world, dev, rank, use_graph=not args.eager)
     value, ms_per_step, n_corr, out = main["value"], main["ms_per_step"], main["n_corr"], main["out"]
-    roofline = conv_roofline(net, x, args.steps, args.precision, ms_per_step, args.layer_report, rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_arrays(*main["step_out"]))
+    del main["step_out"]
+    full = args.full  # every leg below is an extra: a plain run goes straight to the result line
+    roofline = None
+    if full or args.layer_report:
+        roofline = conv_roofline(net, x, args.steps, args.precision, ms_per_step, args.layer_report, rank)
 
     # (the training leg runs right after the headline: measured inside the full bench after the bf16
     # and bs=1 hipGraph legs with the world-size-1 RCCL group alive, the same step read ~1 ms slower
@@ -635,7 +685,7 @@ def run(args):
     # RCCL group (rccl_world1): every bucket's all_reduce is a real RCCL collective on its stream.
     train = None
     tprec = "bf16"
-    if not args.no_train:
+    if full and not args.no_train:
         from zebrapose_amd.train import TrainStep
         tnet = BinaryCodeNet_Deeplab(34, 16, 2, concat=True, output_kernel_size=1, precision=tprec).to(dev)
         calibrate_bn(tnet, x)
@@ -704,7 +754,7 @@ def run(args):
     # the same step with bf16 storage / bf16 MFMA (f32 accumulate): narrower than the reference's
     # fp32, so a labelled extra with its own roofline, not the headline
     bf16 = None
-    if args.precision != "bf16" and not args.no_bf16:
+    if full and args.precision != "bf16" and not args.no_bf16:
         net.set_precision("bf16")
         r = time_infer(net, x, dec, bboxes, args.steps, args.warmup, world, dev, rank, use_graph=not args.eager)
         bf16 = {"crops_per_s": round(r["value"], 2), "ms_per_step": round(r["ms_per_step"], 3), "dtype": "bf16",
@@ -715,7 +765,7 @@ def run(args):
 
     # ------------------------------------------------------------------ bs=1 latency: eager vs hipGraph
     bs1 = None
-    if not args.no_bs1 and rank == 0:
+    if full and not args.no_bs1 and rank == 0:
         bs1 = bs1_leg(net, dec, S, dev)
         bs1["dtype"] = args.precision
         # the benched batch launched eagerly, one launch at a time (value is the graph replay)
@@ -731,85 +781,88 @@ def run(args):
         bs1["bs%d_eager_ms_per_step" % B] = round(ele / args.steps * 1e3, 3)
 
     # ------------------------------------------------------------------ on-device PnP (extra, §8f rank 1)
-    # RANSAC-EPnP (150 iterations, 2 px) over the last step's decoded correspondences; the random
-    # network gives random correspondences, i.e. the worst case (no early RANSAC termination)
-    from zebrapose_amd.pnp import PnP
-    pnp = PnP()
-    counts, xy, xyz = out
-    pnp(counts, xy, xyz)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(5):
+    pnp_res = crop_res = None
+    if full:
+        # RANSAC-EPnP (150 iterations, 2 px) over the last step's decoded correspondences; the random
+        # network gives random correspondences, i.e. the worst case (no early RANSAC termination)
+        from zebrapose_amd.pnp import PnP
+        pnp = PnP()
+        counts, xy, xyz = out
         pnp(counts, xy, xyz)
-    e1.record()
-    torch.cuda.synchronize()
-    pnp_ms = e0.elapsed_time(e1) / 5
-    pnp_res = {"ms_per_batch": round(pnp_ms, 3), "crops_per_s": round(B / (pnp_ms * 1e-3), 1), "iterations": 150,
-               "correspondences_per_crop": round(n_corr / B),
-               "what": "the random network's decoded correspondences: no RANSAC early termination (worst case)"}
-    # the same on realistic scenes: 32 crops of 7000 correspondences from a known pose (0.5 px
-    # noise, 30% outliers) -- OpenCV's adaptive bound stops RANSAC after ~25 iterations
-    g = torch.Generator().manual_seed(7)
-    ns, HWs = 7000, 7000
-    Kc = torch.tensor([[572.4114, 0.0, 325.2611], [0.0, 573.57043, 242.04899], [0.0, 0.0, 1.0]], dtype=torch.float64)
-    sc_xy = torch.zeros(B, HWs, 2, dtype=torch.int32)
-    sc_xyz = torch.zeros(B, HWs, 3, dtype=torch.float32)
-    for b in range(B):
-        ang = torch.randn(3, generator=g, dtype=torch.float64) * 0.6
-        th = float(ang.norm())
-        kx = torch.tensor([[0, -ang[2], ang[1]], [ang[2], 0, -ang[0]], [-ang[1], ang[0], 0]], dtype=torch.float64) / th
-        Rm = torch.eye(3, dtype=torch.float64) + np.sin(th) * kx + (1 - np.cos(th)) * kx @ kx
-        tv = torch.tensor([0.0, 0.0, 800.0], dtype=torch.float64) + torch.rand(3, generator=g, dtype=torch.float64) * 100 - 50
-        pw = torch.rand(ns, 3, generator=g, dtype=torch.float64) * 120 - 60
-        Xc = pw @ Rm.T + tv
-        uv = torch.stack([Kc[0, 0] * Xc[:, 0] / Xc[:, 2] + Kc[0, 2], Kc[1, 1] * Xc[:, 1] / Xc[:, 2] + Kc[1, 2]], 1)
-        uv = uv + torch.randn(uv.shape, generator=g, dtype=torch.float64) * 0.5
-        outl = torch.rand(ns, generator=g) < 0.3
-        uv[outl] += torch.rand(int(outl.sum()), 2, generator=g, dtype=torch.float64) * 240 - 120
-        sc_xy[b] = uv.round().int()
-        sc_xyz[b] = pw.float()
-    sc = (torch.full((B,), ns, dtype=torch.int32, device=dev), sc_xy.to(dev), sc_xyz.to(dev))
-    pnp(*sc, Kc.numpy())
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(5):
-        r_sc = pnp(*sc, Kc.numpy())
-    e1.record()
-    torch.cuda.synchronize()
-    sc_ms = e0.elapsed_time(e1) / 5
-    pnp_res["scenes"] = {"ms_per_batch": round(sc_ms, 3), "crops_per_s": round(B / (sc_ms * 1e-3), 1),
-                         "correspondences_per_crop": ns, "outliers": 0.3, "success": int(r_sc[2].sum().item()),
-                         "what": "synthetic scenes from a known pose (0.5 px noise, 30% outliers): RANSAC stops early"}
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(5):
+            pnp(counts, xy, xyz)
+        e1.record()
+        torch.cuda.synchronize()
+        pnp_ms = e0.elapsed_time(e1) / 5
+        pnp_res = {"ms_per_batch": round(pnp_ms, 3), "crops_per_s": round(B / (pnp_ms * 1e-3), 1), "iterations": 150,
+                   "correspondences_per_crop": round(n_corr / B),
+                   "what": "the random network's decoded correspondences: no RANSAC early termination (worst case)"}
+        # the same on realistic scenes: 32 crops of 7000 correspondences from a known pose (0.5 px
+        # noise, 30% outliers) -- OpenCV's adaptive bound stops RANSAC after ~25 iterations
+        g = torch.Generator().manual_seed(7)
+        ns, HWs = 7000, 7000
+        Kc = torch.tensor([[572.4114, 0.0, 325.2611], [0.0, 573.57043, 242.04899], [0.0, 0.0, 1.0]], dtype=torch.float64)
+        sc_xy = torch.zeros(B, HWs, 2, dtype=torch.int32)
+        sc_xyz = torch.zeros(B, HWs, 3, dtype=torch.float32)
+        for b in range(B):
+            ang = torch.randn(3, generator=g, dtype=torch.float64) * 0.6
+            th = float(ang.norm())
+            kx = torch.tensor([[0, -ang[2], ang[1]], [ang[2], 0, -ang[0]], [-ang[1], ang[0], 0]], dtype=torch.float64) / th
+            Rm = torch.eye(3, dtype=torch.float64) + np.sin(th) * kx + (1 - np.cos(th)) * kx @ kx
+            tv = torch.tensor([0.0, 0.0, 800.0], dtype=torch.float64) + torch.rand(3, generator=g, dtype=torch.float64) * 100 - 50
+            pw = torch.rand(ns, 3, generator=g, dtype=torch.float64) * 120 - 60
+            Xc = pw @ Rm.T + tv
+            uv = torch.stack([Kc[0, 0] * Xc[:, 0] / Xc[:, 2] + Kc[0, 2], Kc[1, 1] * Xc[:, 1] / Xc[:, 2] + Kc[1, 2]], 1)
+            uv = uv + torch.randn(uv.shape, generator=g, dtype=torch.float64) * 0.5
+            outl = torch.rand(ns, generator=g) < 0.3
+            uv[outl] += torch.rand(int(outl.sum()), 2, generator=g, dtype=torch.float64) * 240 - 120
+            sc_xy[b] = uv.round().int()
+            sc_xyz[b] = pw.float()
+        sc = (torch.full((B,), ns, dtype=torch.int32, device=dev), sc_xy.to(dev), sc_xyz.to(dev))
+        pnp(*sc, Kc.numpy())
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(5):
+            r_sc = pnp(*sc, Kc.numpy())
+        e1.record()
+        torch.cuda.synchronize()
+        sc_ms = e0.elapsed_time(e1) / 5
+        pnp_res["scenes"] = {"ms_per_batch": round(sc_ms, 3), "crops_per_s": round(B / (sc_ms * 1e-3), 1),
+                             "correspondences_per_crop": ns, "outliers": 0.3, "success": int(r_sc[2].sum().item()),
+                             "what": "synthetic scenes from a known pose (0.5 px noise, 30% outliers): RANSAC stops early"}
 
     # ------------------------------------------------------------------ device crop pipeline (extra, §8f rank 2)
-    from zebrapose_amd.crop import CropPipeline
-    cp = CropPipeline()
-    g = torch.Generator(device="cpu").manual_seed(3)
-    imgs = torch.randint(0, 256, (8, 480, 640, 3), generator=g, dtype=torch.uint8).to(dev)
-    gts = torch.randint(0, 256, (8, 480, 640, 3), generator=g, dtype=torch.uint8).to(dev)
-    msk = torch.randint(0, 256, (8, 480, 640), generator=g, dtype=torch.uint8).to(dev)
-    raw = np.stack([rng.integers(0, 500, B), rng.integers(0, 350, B), rng.integers(40, 200, B),
-                    rng.integers(40, 200, B)], 1)
-    pad, _ = cp.boxes(raw, 640, 480)
-    cidx = np.arange(B) % 8
-    cp(imgs, cidx, pad, gts, msk, msk)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(10):
+    if full:
+        from zebrapose_amd.crop import CropPipeline
+        cp = CropPipeline()
+        g = torch.Generator(device="cpu").manual_seed(3)
+        imgs = torch.randint(0, 256, (8, 480, 640, 3), generator=g, dtype=torch.uint8).to(dev)
+        gts = torch.randint(0, 256, (8, 480, 640, 3), generator=g, dtype=torch.uint8).to(dev)
+        msk = torch.randint(0, 256, (8, 480, 640), generator=g, dtype=torch.uint8).to(dev)
+        raw = np.stack([rng.integers(0, 500, B), rng.integers(0, 350, B), rng.integers(40, 200, B),
+                        rng.integers(40, 200, B)], 1)
+        pad, _ = cp.boxes(raw, 640, 480)
+        cidx = np.arange(B) % 8
         cp(imgs, cidx, pad, gts, msk, msk)
-    e1.record()
-    torch.cuda.synchronize()
-    crop_ms = e0.elapsed_time(e1) / 10
-    crop_res = {"ms_per_batch": round(crop_ms, 3), "crops_per_s": round(B / (crop_ms * 1e-3), 1),
-                "what": "640x480 BGR images -> 256 px INTER_LINEAR normalised crop + 128 px GT code planes and "
-                        "2 masks (INTER_NEAREST), padding 1.5"}
-    del imgs, gts, msk
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(10):
+            cp(imgs, cidx, pad, gts, msk, msk)
+        e1.record()
+        torch.cuda.synchronize()
+        crop_ms = e0.elapsed_time(e1) / 10
+        crop_res = {"ms_per_batch": round(crop_ms, 3), "crops_per_s": round(B / (crop_ms * 1e-3), 1),
+                    "what": "640x480 BGR images -> 256 px INTER_LINEAR normalised crop + 128 px GT code planes and "
+                            "2 masks (INTER_NEAREST), padding 1.5"}
+        del imgs, gts, msk
 
     # ------------------------------------------------------------------ 3-head v3 network (extra, §8f rank 3)
     v3 = None
-    if not args.no_train:
+    if full and not args.no_train:
         from zebrapose_amd.model.BinaryCodeNet_v3 import BinaryCodeNet_Deeplab_v3
         from zebrapose_amd.train import TrainStep
         n3 = BinaryCodeNet_Deeplab_v3(34, 16, 2, concat=True, output_kernel_size=1, precision=tprec).to(dev)
@@ -845,12 +898,12 @@ def run(args):
 
     # ------------------------------------------------------------------ configs[4] multi-object leg (extra)
     multi = None
-    if rank == 0 and world == 1 and not args.no_multi:
+    if full and rank == 0 and world == 1 and not args.no_multi:
         multi = multi_object_leg(args, dev)
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N = 1)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(args, net, x, bboxes)
 
     if rank == 0:

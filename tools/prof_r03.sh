@@ -19,7 +19,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 D="python3 tools/prof_driver.py --mode infer --steps 3 --warmup 2"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- \
-    python3 bench.py --no-train --no-cpu --no-multi --no-bs1 --steps 10 --warmup 3 > $O/stats.log 2>&1
+    python3 bench.py --full --no-train --no-cpu --no-multi --no-bs1 --steps 10 --warmup 3 > $O/stats.log 2>&1
 echo "stats ok"
 for P in $PRECS; do
   timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d $O/trace_$P -o run -- \
