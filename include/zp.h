@@ -181,15 +181,18 @@ long long zp_conv2d_split_ws(const zp_conv_args* a);
  * 128-channel tiles with (fewer: 64-channel tiles); key 9 = split-K of small split-fp32 launches
  * (default 1, 0 off); keys 10-12 = the 256 x 256 two-plane tile (on / fewest workgroups / split-K);
  * key 13 = its accumulation form (0 the flushed correction accumulator, default; 1 one scaled
- * accumulator; 2 per-step partial sums; 3 flushed on the 2^11 scale); key 14 = its 256 x 128 tile
- * (default 0); key 15 = zp_bn_train_finalize's merge in one launch (1, default) or two (0); key 16 =
- * k_conv3's multi-sub launches with a tile's subs adjacent on one XCD (default 0); key 17 = k_conv3w's
- * multi-sub launches (ConvT phases) with a pixel tile's phases adjacent on one XCD (default 0); key 18
+ * accumulator; 2 per-step partial sums; 3 flushed on the 2^11 scale; 4 a persistent second
+ * accumulator); key 14 = its 256 x 128 tile (default 0); key 15 = zp_bn_train_finalize's merge in
+ * one launch (1, default) or two (0); key 16 = k_conv3's multi-sub launches with a tile's subs
+ * adjacent on one XCD (default 0); key 17 = k_conv3w's multi-sub launches (ConvT phases) with a
+ * pixel tile's phases adjacent on one XCD (default 0); key 18
  * = the 256 x 256 two-plane tile on 32x32x16 MFMAs (default 0); key 19 = the ring depth (2, 3, 4) of
  * the register-pipelined two-plane 64-channel tile (default 2); key 20 = persistent workgroups per CU
  * of the two-plane stem (1 or 2, default 1); key 21 = the wide strip tile's next-step pixel fragments
- * read before the step's barrier (1, default) or after it (0).  Returns the previous value, -1 for an
- * unknown key. */
+ * read before the step's barrier (1, default) or after it (0).  Keys 7, 10 and 13-21 hold -1 until
+ * set: the environment (ZP_CONV3_STRIP, ZP_CONV3W, ZP_CONV3W_ACC, ZP_CONV3W_TP128, ZP_BN_FUSED,
+ * ZP_CONV3_SUBINT, ZP_CONV3W_SUBINT, ZP_CONV3W_MF32, ZP_CONV3_PIPE_ST, ZP_STEM_WGS, ZP_CONV3W_PFB) or
+ * the default then decides.  Returns the previous value, -1 for an unknown key. */
 int zp_conv_tuning(int key, int value);
 
 /* Fused 1x1 head (the reference's conv_1x1_4 over torch.cat([x, x_128]) and the mask / code split,

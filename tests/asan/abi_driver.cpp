@@ -98,6 +98,40 @@ int main() {
   zp_conv_args bnr2 = conv(ZP_BF16, 32, 128, 128, 256, 256, 3, 1);  // strip tile: one part per 256 pixels
   CHECK(zp_conv2d_bnr_parts(&bnr2) == 32 * 128 * 128 / 256);
   CHECK(zp_conv2d_bnr_parts(&bnr2) == zp_conv2d_stat_parts(&bnr2));       // (the statistics too, round 5)
+  // one geometry per launch plan (tests/test_conv_plan.py pins the whole table)
+  zp_conv_args strip = conv(ZP_BF16, 32, 64, 64, 128, 128, 3, 1);
+  CHECK(zp_conv2d_config(&strip, &tc, &tp, &st, &var) == ZP_OK && var == 2 && tc == 128 && tp == 256);
+  CHECK(zp_conv2d_grid(&strip) == 32 * 64 * 64 / 256);
+  CHECK(zp_conv2d_stat_parts(&strip) == zp_conv2d_grid(&strip));     // wave halves merged in LDS
+  CHECK(zp_conv2d_bnr_parts(&strip) <= zp_conv2d_stat_parts(&strip));
+  zp_conv_args quad = conv(ZP_BF16, 32, 64, 64, 256, 256, 1, 1);      // ConvT(3, s2, p1, op1): four phases
+  quad.nsub = 4; quad.k_pad = 4 * 256;
+  for (int s = 0; s < 4; ++s) {
+    zp_conv_sub& S = quad.sub[s];
+    S = quad.sub[0];
+    S.OH = S.OW = 128; S.oys = S.oxs = 2; S.oyo = s / 2; S.oxo = s % 2; S.ntaps = 0;
+    for (int ky = 0; ky < 3; ++ky)
+      for (int kx = 0; kx < 3; ++kx)
+        if ((ky - s / 2 - 1) % 2 == 0 && (kx - s % 2 - 1) % 2 == 0) {
+          S.ty[S.ntaps] = (signed char)((s / 2 + 1 - ky) / 2);
+          S.tx[S.ntaps++] = (signed char)((s % 2 + 1 - kx) / 2);
+        }
+  }
+  CHECK(zp_conv2d_config(&quad, &tc, &tp, &st, &var) == ZP_OK && var == 3 && tc == 64 && tp == 256);
+  CHECK(zp_conv2d_stat_parts(&quad) == 4 * zp_conv2d_grid(&quad));    // one part per tile and phase
+  CHECK(zp_conv2d_bnr_parts(&quad) <= zp_conv2d_stat_parts(&quad));
+  zp_conv_args c1n = conv(ZP_BF16, 32, 128, 128, 32, 320, 1, 1);      // the head's data gradient
+  c1n.k_pad = 64;
+  CHECK(zp_conv2d_config(&c1n, &tc, &tp, &st, &var) == ZP_OK && var == 7);
+  CHECK(zp_conv2d_bnr_parts(&c1n) <= zp_conv2d_stat_parts(&c1n));
+  zp_conv_args gen = conv(ZP_BF16, 4, 16, 16, 64, 128, 1, 1);
+  CHECK(zp_conv2d_config(&gen, &tc, &tp, &st, &var) == ZP_OK && var == 0 && tc == 128 && st == 3);
+  CHECK(zp_conv2d_grid(&gen) == (4 * 16 * 16 + tp - 1) / tp);
+  CHECK(zp_conv2d_stat_parts(&gen) == zp_conv2d_grid(&gen));
+  CHECK(zp_conv2d_bnr_parts(&gen) <= zp_conv2d_stat_parts(&gen));
+  CHECK(zp_conv2d_head_ok(&gen) == 0 && zp_conv2d_split_ws(&gen) == 0);
+  // [splits][Cout][9 * Cin] f32: one round of 128 x 256 tiles over 256 CUs, 256 / 18 = 14 splits
+  CHECK(zp_conv2d_wgrad_ws_bytes(&wa) == 14LL * 256 * 9 * 256 * 4);
   // tuning knobs round-trip; unknown keys answer -1
   const int old = zp_conv_tuning(10, 0);
   CHECK(zp_conv_tuning(10, old) == 0);

@@ -52,7 +52,8 @@ def _kernel_metadata_from_sources(tmp_path):
     """The same from the sources: device code of every conv source compiled to assembly with the
     Makefile's per-file flags."""
     import re
-    srcs = {"zp_conv.hip": [], "zp_conv3.hip": [], "zp_conv3w.hip": ["-fno-slp-vectorize"], "zp_stem.hip": []}
+    srcs = {"zp_conv.hip": [], "zp_wgrad.hip": [], "zp_conv3.hip": [], "zp_conv3w.hip": ["-fno-slp-vectorize"],
+            "zp_stem.hip": []}
     procs = []
     for f, extra in srcs.items():
         asm = tmp_path / (f + ".s")

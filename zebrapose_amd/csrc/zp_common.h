@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 #include "../../include/zp.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -135,5 +136,23 @@ template <> struct H16<f16_t> {
 };
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// integer environment override (0 when unset)
+inline int env_int(const char* name) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : 0;
+}
+
+// compute units of the current device (256, the MI355X's, when there is none to ask)
+inline int num_cus() {
+  static int n = 0;
+  if (!n) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        n <= 0)
+      n = 256;
+  }
+  return n;
+}
 
 }  // namespace zp

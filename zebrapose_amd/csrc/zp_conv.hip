@@ -1,5 +1,6 @@
-// Implicit-GEMM convolution for gfx950 (MI355X): forward / data-gradient (k_conv)
-// and weight-gradient (k_wgrad).  NHWC activations, packed [rows][tap*Cin] weights.
+// Implicit-GEMM convolution for gfx950 (MI355X): forward / data-gradient (k_conv) in f32 / bf16 /
+// fp16 (the weight gradient: zp_wgrad.hip; split fp32: zp_conv3*.hip).  NHWC activations, packed
+// [rows][tap*Cin] weights.
 //
 // Replaces the cuDNN convolutions behind nn.Conv2d / nn.ConvTranspose2d at
 // model/resnet.py:41-51, model/aspp.py:60-80, 89-112 and the torchvision ResNet
@@ -13,16 +14,6 @@
 // ring (XOR-swizzled 16 B chunks, one barrier per K step).
 #include <type_traits>
 #include "zp_common.h"
-
-// Diagnostic ablation builds only (tools/build_ablation.sh -> libzp_abl<N>.so; wrong results):
-// ZP_ABL 1 = k_conv / k_conv_strip / k_wgrad_lds issue no LDS-DMA, 2 = they run no MFMA, 3 = k_conv
-// / k_conv_strip stage only the weights (no activation DMA), 4 = k_conv_strip stages only the strips,
-// 6 = the 16-bit NHWC epilogue stores nothing, 7 = it loads no BN scale / shift.
-// The product build is ZP_ABL 0.
-#ifndef ZP_ABL
-#define ZP_ABL 0
-#endif
-
 #include "zp_conv_kern.h"
 #include "zp_conv3.h"
 
@@ -1779,13 +1770,6 @@ __global__ void __launch_bounds__(512) k_conv_quad(const zp_conv_args A, const q
 }
 
 // ------------------------------------------------------------------------------------
-// Tiny-M 1x1 convs without statistics or residual (the ASPP image-pool conv, aspp.py:94-96: B
-// pixels of a 1x1 image, 512 -> 256 channels).  One wave computes 16 output channels of one pixel:
-// lanes split K into 16-byte chunks (coalesced 1 KB weight-row reads), f32 products, a butterfly
-// sum over the 64 lanes, and k_conv's epilogue arithmetic (scale / shift, ReLU).  Opt-in (conv flag
-// 1024): measured 16.8 vs 17.7 us per eager launch, i.e. both are launch latency, which the
-// hipGraph-replayed inference step does not pay; the network tests pass with it enabled.
-// ------------------------------------------------------------------------------------
 // 1 x 1 conv with a narrow K and a wide output (the head's data gradient in training: 32 -> 320
 // channels at 128 x 128, bs 32 -- 34 MB in, 335 MB out).  On k_conv's small-Cin tile it took 177 us
 // (2.1 TB/s): one K step per 128 x 256 tile, so every workgroup was prologue + epilogue at one
@@ -1845,879 +1829,17 @@ __global__ void __launch_bounds__(256) k_conv1x1n(const zp_conv_args A) {
   }
 }
 
-template <typename T>
-__device__ __forceinline__ void ld16x8(const T* p, float* v) {  // 8 16-bit values, one 16-byte load
-  const uint4 u = *(const uint4*)p;
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = H16<T>::from(w[i] & 0xffffu);
-    v[2 * i + 1] = H16<T>::from(w[i] >> 16);
-  }
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256) k_conv_smallm(const zp_conv_args A) {
-  const zp_conv_sub& S = A.sub[0];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int m = blockIdx.y;  // grid point
-  const int GHW = A.GH * A.GW;
-  const int n = m / GHW, r = m - n * GHW, gy = r / A.GW, gx = r - gy * A.GW;
-  const int iy = gy * A.sy + S.ty[0], ix = gx * A.sx + S.tx[0];
-  const bool inb = (unsigned)iy < (unsigned)A.IH && (unsigned)ix < (unsigned)A.IW;
-  const T* xr = (const T*)A.x + (((size_t)n * A.IH + (inb ? iy : 0)) * A.IW + (inb ? ix : 0)) * A.ldx + A.cx0;
-  const int oy = gy * S.oys + S.oyo, ox = gx * S.oxs + S.oxo;
-  const size_t pix = ((size_t)n * S.OH + oy) * S.OW + ox;
-  const int co0 = blockIdx.x * 64 + w * 16;
-  float acc[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-  for (int k0 = lane * 8; k0 < A.Cin; k0 += 512) {
-    float xv[8];
-    ld16x8<T>(xr + k0, xv);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) xv[i] = inb ? xv[i] : 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      float wv[8];
-      ld16x8<T>((const T*)S.w + (size_t)(co0 + q) * A.k_pad + k0, wv);  // rows < w_rows (host check)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc[q] = fmaf(xv[i], wv[i], acc[q]);
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 16; ++q)
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) acc[q] += __shfl_xor(acc[q], off);
-  if (lane < 16) {
-    float v = acc[0];
-#pragma unroll
-    for (int q = 1; q < 16; ++q) v = lane == q ? acc[q] : v;
-    const int co = co0 + lane;
-    if (co < A.Cout) {
-      const float sc = S.scale ? S.scale[co] : 1.f, sh = S.shift ? S.shift[co] : 0.f;
-      v = v * sc + sh;
-      if (A.relu) v = fmaxf(v, 0.f);
-      ((T*)S.y)[pix * S.ldy + S.cy0 + co] = Elem<T>::cvt(v);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------
-// weight gradient:  ws[split][sub][co][col] = sum over the split's grid points of
-//   dy[out pixel][co] * x[in pixel (tap of col)][ci of col],   col = t*Cin + ci
-// K (pixels) is the MFMA reduction axis, so both LDS tiles [pixel][channel] are read
-// transposed with ds_read_b64_tr_b16 (bf16) / per-lane b32 (f32).
-// ------------------------------------------------------------------------------------
-template <typename T> struct WgTraits;
-template <> struct WgTraits<bf16_t> { static constexpr int KP = 32; };  // pixels per K step
-template <> struct WgTraits<float> { static constexpr int KP = 16; };
-
-constexpr int WG_TILE = 128;            // co x col tile
-constexpr int WG_ROWB = 256 + 16;       // LDS row bytes (128 ch of bf16 / 64 of f32 -> see below)
-
-template <typename T>
-__global__ void __launch_bounds__(256) k_wgrad(const zp_wgrad_args A, float* __restrict__ ws, int pix_per_split,
-                                                int col_tiles, int cols_max) {
-  constexpr int KP = WgTraits<T>::KP;
-  constexpr int CHE = 16 / sizeof(T);            // elements per 16 B chunk
-  constexpr int NCH = WG_TILE / CHE;             // chunks per 128-channel row (16 bf16 / 32 f32)
-  constexpr int ROWB = WG_TILE * sizeof(T) + 16; // padded LDS row bytes
-  constexpr int TILEB = KP * ROWB;
-  constexpr int LPT = KP * NCH / 256;            // chunk loads per thread per tile (2)
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][TILEB];
-
-  const int sub = blockIdx.z;
-  const auto& S = A.sub[sub];
-  const int cols = S.ntaps * A.Cin;
-  const int ct = blockIdx.y % col_tiles, cot = blockIdx.y / col_tiles;
-  const int col0 = ct * WG_TILE, co0 = cot * WG_TILE;
-  if (col0 >= cols) return;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wc = wid >> 1, wk = wid & 1;
-  const int GHW = A.GH * A.GW;
-  const int M = A.N * GHW;
-  const int pbeg = blockIdx.x * pix_per_split;
-  const int pend = min(M, pbeg + pix_per_split);
-
-  // thread -> (row, chunk) of both tiles; chunk column fixed for the whole kernel
-  const int qc = tid % NCH, qr = tid / NCH;      // rows qr + (256/NCH)*i
-  constexpr int RSTEP = 256 / NCH;
-  // dy channel of this chunk
-  const int dco = co0 + qc * CHE;
-  const bool dco_ok = dco < A.Cout;
-  // x column of this chunk -> (tap, ci)
-  const int xcol = col0 + qc * CHE;
-  const bool xcol_ok = xcol < cols;
-  const int xt = xcol_ok ? xcol / A.Cin : 0;
-  const int xci = xcol - xt * A.Cin;
-  const int xty = S.ty[xt], xtx = S.tx[xt];
-  const T* __restrict__ X = (const T*)A.x;
-  const T* __restrict__ DY = (const T*)S.dy;
-
-  uint4 rd[LPT], rx[LPT];
-  auto gload = [&](int pk) {
-#pragma unroll
-    for (int i = 0; i < LPT; ++i) {
-      int p = pk + qr + RSTEP * i;
-      uint4 vd = make_uint4(0, 0, 0, 0), vx = make_uint4(0, 0, 0, 0);
-      if (p < pend) {
-        int n = p / GHW, rr = p - n * GHW;
-        int gy = rr / A.GW, gx = rr - gy * A.GW;
-        if (dco_ok) {
-          int oy = gy * S.oys + S.oyo, ox = gx * S.oxs + S.oxo;
-          vd = *(const uint4*)(DY + (((size_t)n * S.OH + oy) * S.OW + ox) * S.lddy + S.cdy0 + dco);
-        }
-        int iy = gy * A.sy + xty, ix = gx * A.sx + xtx;
-        if (xcol_ok && (unsigned)iy < (unsigned)A.IH && (unsigned)ix < (unsigned)A.IW)
-          vx = *(const uint4*)(X + (((size_t)n * A.IH + iy) * A.IW + ix) * A.ldx + A.cx0 + xci);
-      }
-      rd[i] = vd;
-      rx[i] = vx;
-    }
-  };
-  auto sstore = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < LPT; ++i) {
-      int row = qr + RSTEP * i;
-      *(uint4*)(&lds[buf][0][row * ROWB + qc * 16]) = rd[i];
-      *(uint4*)(&lds[buf][1][row * ROWB + qc * 16]) = rx[i];
-    }
-  };
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const int nsteps = pend > pbeg ? (pend - pbeg + KP - 1) / KP : 0;
-  if (nsteps > 0) {
-    gload(pbeg);
-    sstore(0);
-  }
-  __syncthreads();
-  for (int s = 0; s < nsteps; ++s) {
-    const int buf = s & 1;
-    if (s + 1 < nsteps) gload(pbeg + (s + 1) * KP);
-    const unsigned char* TD = lds[buf][0];
-    const unsigned char* TX = lds[buf][1];
-    if constexpr (sizeof(T) == 2) {
-      // A[co][k] and B[k][col]: lane l of group g = l>>4 needs k = 8g..8g+7 of column (l & 15)
-      typedef __attribute__((ext_vector_type(4))) short s4;
-      const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
-      bf16x8 af[4], bfm[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int cbase = wc * 64 + i * 16 + 4 * pp;
-        const unsigned char* a0 = TD + (8 * g + q) * ROWB + cbase * 2;
-        s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(a0));
-        s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(a0 + 4 * ROWB));
-        typedef __attribute__((ext_vector_type(8))) short s8;
-        s8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        af[i] = __builtin_bit_cast(bf16x8, v);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        int cbase = wk * 64 + j * 16 + 4 * pp;
-        const unsigned char* b0 = TX + (8 * g + q) * ROWB + cbase * 2;
-        s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(b0));
-        s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(b0 + 4 * ROWB));
-        typedef __attribute__((ext_vector_type(8))) short s8;
-        s8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        bfm[j] = __builtin_bit_cast(bf16x8, v);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfm[j], acc[i][j], 0, 0, 0);
-    } else {
-      // f32: A[i=l&15][k=l>>4], B[k=l>>4][j=l&15]; 4 MFMAs of K=4 per 16-pixel step
-      const int li = lane & 15, g = lane >> 4;
-#pragma unroll
-      for (int kk = 0; kk < KP; kk += 4) {
-        float av[4], bv[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          av[i] = *(const float*)(TD + (kk + g) * ROWB + (wc * 64 + i * 16 + li) * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          bv[j] = *(const float*)(TX + (kk + g) * ROWB + (wk * 64 + j * 16 + li) * 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-      }
-    }
-    if (s + 1 < nsteps) sstore(buf ^ 1);
-    __syncthreads();
-  }
-  // write partial tile: ws[((split*nsub + sub)*Cout + co)*cols_max + col]
-  float* W = ws + ((size_t)blockIdx.x * A.nsub + sub) * (size_t)A.Cout * cols_max;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int col = col0 + wk * 64 + j * 16 + (lane & 15);
-      if (col >= cols) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int co = co0 + wc * 64 + i * 16 + (lane >> 4) * 4 + r;
-        if (co < A.Cout) W[(size_t)co * cols_max + col] = acc[i][j][r];
-      }
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// bf16 weight gradient, LDS-DMA version.  Same product and workspace layout as k_wgrad.
-//
-// A workgroup of 8 waves owns a (64*NA output channels) x (64*NB columns) tile; wave
-// (a, b) = (w / NB, w % NB) computes a 64 x 64 block with 4 x 4 v_mfma_f32_16x16x32_bf16.
-// Every K step covers KP consecutive grid points (pixels).  The stage image is NA + NB
-// "panels" of [KP pixel rows][64 channels] (128 B rows): panels 0..NA-1 hold dy channels,
-// panels NA.. hold x columns (tap, channel).  They are filled straight from global memory by
-// buffer_load ... lds (one wave-instruction = 8 rows), STAGES-deep ring, counted vmcnt + raw
-// barrier per step, exactly as k_conv does.
-//
-// The MFMA reduces over pixels, so both operands are read transposed with
-// ds_read_b64_tr_b16: lane 4q+p of 16-lane group g supplies row (8g + q) and columns
-// 4p..4p+3 of a 16-column block and receives one column (4 consecutive pixels).  Chunk
-// swizzle: the 16 B chunk c of row R sits at chunk c ^ s(R), s(R) = 2 * (bit1(R) | bit3(R) << 1)
-// (even, so the chunk pair of a 16-column block stays adjacent): the 8 rows a 32-lane half
-// reads (two groups, rows 8g+q, q < 4) then cover all 64 banks once -- conflict-free.  The
-// LDS-DMA writes are lane-linear, so the swizzle is applied on the per-lane SOURCE chunk.
-//
-// The tap walk is per lane: each lane always loads the same pixel row R of the tile (the
-// instruction -> row-block map is wave-constant), so the grid point (n, gy, gx) advances
-// incrementally by KP per issued step -- no divisions in the loop.
-// ------------------------------------------------------------------------------------
-struct wg_bounds {
-  unsigned x_bytes, dy_bytes[ZP_MAX_SUB];
-};
-
-__device__ __forceinline__ int wg_swz(int r) { return (((r >> 1) & 1) | (((r >> 3) & 1) << 1)) << 1; }
-
-template <int OFF>
-__device__ __forceinline__ uint2 ds_read_tr8(unsigned addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds offset range");
-  uint2 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-  return r;
-}
-
-template <int KP, int NA, int NB, int STAGES, int WN>
-__global__ void __launch_bounds__(512) k_wgrad_lds(const zp_wgrad_args A, float* __restrict__ ws, int pix_per_split,
-                                                   int col_tiles, int tiles_per_sub, int cols_max,
-                                                   const wg_bounds WB) {
-  static_assert(NA * NB == 8 * WN, "8 waves of 64 x (64 WN)");
-  constexpr int NBW = NB / WN;           // wave columns
-  static_assert(KP == 32 || KP == 64, "K step");
-  static_assert(STAGES == 2 || STAGES == 3, "ring depth");
-  constexpr int NP = NA + NB;            // panels per stage
-  constexpr int PB = KP * 128;           // panel bytes
-  constexpr int SB = NP * PB;            // stage bytes
-  constexpr int IPP = KP / 8;            // wave-instructions per panel
-  constexpr int NI = NP * IPP;           // wave-instructions per stage
-  constexpr int JPW = (NI + 7) / 8;      // per wave (the last may be idle)
-  static_assert(SB * STAGES <= 160 * 1024, "LDS");
-  __shared__ uint4 lds0[SB / 16];
-  __shared__ uint4 lds1[SB / 16];
-  __shared__ uint4 lds2[STAGES == 3 ? SB / 16 : 1];
-  auto bufp = [&](auto i_c) -> uint4* {
-    constexpr int i = decltype(i_c)::value;
-    if constexpr (i == 0) return lds0;
-    else if constexpr (i == 1) return lds1;
-    else return lds2;
-  };
-
-  // 1-D grid, XCD-aware: workgroups are dispatched round-robin over the 8 XCDs (separate L2s);
-  // remap so that each XCD walks a contiguous range of (split, sub, tile) with the tiles
-  // fastest -- every tile of one split reads the same dy / x pixel rows, which then meet in one
-  // L2 instead of being fetched by all eight.
-  const int total = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, pos = bid >> 3, q8 = total >> 3, r8 = total & 7;  // bijective for any total
-  const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
-  const int tiles = tiles_per_sub;
-  const int tile = lin % tiles;
-  const int rest = lin / tiles;
-  const int sub = rest % A.nsub;
-  const int split = rest / A.nsub;
-  const auto& S = A.sub[sub];
-  const int cols = S.ntaps * A.Cin;
-  const int ct = tile % col_tiles, cot = tile / col_tiles;
-  const int col0 = ct * 64 * NB, co0 = cot * 64 * NA;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wa = wid / NBW, wb = wid % NBW;  // wave (co panel, group of WN column panels)
-  const int GHW = A.GH * A.GW;
-  const int M = A.N * GHW;
-  const int pbeg = split * pix_per_split;
-  const int pend = min(M, pbeg + pix_per_split);
-  const int nK = pend > pbeg ? (pend - pbeg + KP - 1) / KP : 0;
-
-  // ---- staging state of this lane: pixel row R, source chunk of every panel
-  const int rowblk = (KP == 64) ? wid : (wid & 3);
-  // panel of this wave's j-th wave-instruction (instruction q = wid + 8 j, IPP per panel)
-  auto panel_of = [&](int j) { return KP == 64 ? j : 2 * j + ((wid >> 2) & 1); };
-  const int R = rowblk * 8 + (lane >> 3);
-  const int lchunk = (lane & 7) ^ wg_swz(R);
-  const int cout8 = (A.Cout + 7) & ~7;
-  int poff[NP];        // per-panel lane offset (bytes; x panels: relative to the pixel base)
-  int pty[NP], ptx[NP];
-  bool pok[NP];
-#pragma unroll
-  for (int P = 0; P < NP; ++P) {
-    if (P < NA) {
-      const int ch = co0 + 64 * P + 8 * lchunk;
-      pok[P] = ch < cout8;
-      poff[P] = (S.cdy0 + ch) * 2;
-      pty[P] = ptx[P] = 0;
-    } else {
-      const int col = col0 + 64 * (P - NA) + 8 * lchunk;
-      pok[P] = col < cols;
-      const int t = pok[P] ? col / A.Cin : 0;
-      const int ci = col - t * A.Cin;
-      pty[P] = S.ty[t];
-      ptx[P] = S.tx[t];
-      poff[P] = ((pty[P] * A.IW + ptx[P]) * A.ldx + A.cx0 + ci) * 2;
-    }
-  }
-  // grid point of the next step to issue
-  int pn, pgy, pgx;
-  {
-    const int p = min(pbeg + R, M - 1);
-    pn = p / GHW;
-    const int rr = p - pn * GHW;
-    pgy = rr / A.GW;
-    pgx = rr - pgy * A.GW;
-  }
-  int pnext = pbeg + R;
-#if defined(__HIP_DEVICE_COMPILE__)
-  const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)A.x, (short)0, (int)WB.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t drsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)S.dy, (short)0, (int)WB.dy_bytes[sub], 0x00020000);
-#endif
-
-  auto issue = [&](uint4* dst) {
-    const bool pv = pnext < pend;
-    const unsigned dbase =
-        (unsigned)((((pn * S.OH + pgy * S.oys + S.oyo) * S.OW + pgx * S.oxs + S.oxo) * S.lddy) * 2);
-    const int iy0 = pgy * A.sy, ix0 = pgx * A.sx;
-    const int xbase = (((pn * A.IH + iy0) * A.IW + ix0) * A.ldx) * 2;
-    unsigned voff[JPW];
-#pragma unroll
-    for (int j = 0; j < JPW; ++j) {
-      const int P = panel_of(j);  // wave-uniform (compile-time for KP 64)
-      voff[j] = 0x80000000u;
-      if (P < NA) {
-        if (pv && pok[P]) voff[j] = dbase + (unsigned)poff[P];
-      } else if (P < NP) {
-        const int iy = iy0 + pty[P], ix = ix0 + ptx[P];
-        if (pv && pok[P] && (unsigned)iy < (unsigned)A.IH && (unsigned)ix < (unsigned)A.IW)
-          voff[j] = (unsigned)(xbase + poff[P]);
-      }
-    }
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-    for (int j = 0; j < JPW; ++j) {
-      const int P = panel_of(j);
-      if (P >= NP) continue;
-      auto* d = (__attribute__((address_space(3))) void*)((unsigned char*)dst + P * PB + rowblk * 1024);
-      if (P < NA) __builtin_amdgcn_raw_ptr_buffer_load_lds(drsrc, d, 16, voff[j], 0, 0, 0);
-      else __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, d, 16, voff[j], 0, 0, 0);
-    }
-#endif
-    pnext += KP;
-    if (A.GW >= 16) {  // at most KP / 16 row wraps per step: predicated, no loop
-      pgx += KP;
-#pragma unroll
-      for (int it = 0; it < KP / 16; ++it) {
-        if (pgx >= A.GW) {
-          pgx -= A.GW;
-          if (++pgy == A.GH) {
-            pgy = 0;
-            ++pn;
-          }
-        }
-      }
-    } else {  // tiny grids (1x1 image-pool branch): divide
-      const int p = min(pnext, M - 1);
-      pn = p / GHW;
-      const int rr = p - pn * GHW;
-      pgy = rr / A.GW;
-      pgx = rr - pgy * A.GW;
-    }
-  };
-
-  f32x4 acc[4][4 * WN];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4 * WN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  // fragment read addresses: lane (g, 4q+p) -> row 8g + q, byte 8p of the 16-column block,
-  // 16-column block ii at chunk pair 2*(ii ^ s'), s' = s(R) / 2 (independent of the +4 / +32
-  // row offsets, which are immediates)
-  const int g = lane >> 4, q4 = (lane >> 2) & 3, p4 = lane & 3;
-  const int sh = (((q4 >> 1) & 1) | ((g & 1) << 1));
-  unsigned ra[4];
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) ra[ii] = (unsigned)(wa * PB) + (unsigned)(128 * (8 * g + q4) + 8 * p4 + 32 * (ii ^ sh));
-  // column panel w of this wave = panel NA + wb * WN + w: an immediate offset w * PB
-
-  auto step = [&](auto cur_c, auto nxt_c, int ks) {
-    const bool more = ks + (STAGES - 1) < nK;
-    if constexpr (ZP_ABL != 1) {
-      if (more) issue(bufp(nxt_c));
-    }
-    const unsigned cb = lds_addr(bufp(cur_c));
-    unsigned pa[4], pb[4];
-#pragma unroll
-    for (int ii = 0; ii < 4; ++ii) {
-      pa[ii] = cb + ra[ii];
-      pb[ii] = pa[ii] + (unsigned)((NA + wb * WN - wa) * PB);
-    }
-    static_for<KP / 32>([&](auto s2) {
-      uint4 af[4], bfr[4 * WN];
-      static_for<4>([&](auto ii) {
-        const uint2 a0 = ds_read_tr8<s2 * 4096>(pa[ii]);
-        const uint2 a1 = ds_read_tr8<s2 * 4096 + 512>(pa[ii]);
-        af[ii] = make_uint4(a0.x, a0.y, a1.x, a1.y);
-        static_for<WN>([&](auto w) {
-          const uint2 b0 = ds_read_tr8<w * PB + s2 * 4096>(pb[ii]);
-          const uint2 b1 = ds_read_tr8<w * PB + s2 * 4096 + 512>(pb[ii]);
-          bfr[w * 4 + ii] = make_uint4(b0.x, b0.y, b1.x, b1.y);
-        });
-      });
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-      if constexpr (ZP_ABL != 2) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4 * WN; ++j) MfmaTraits<bf16_t>::mma(acc[i][j], af[i], bfr[j]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i][0][0] += __uint_as_float(af[i].x ^ bfr[i].y);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(0);
-    });
-    if (more) vm_wait<JPW * (STAGES - 2)>();
-    else vm_wait<0>();
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-  if (nK > 0) {
-    issue(lds0);
-    if (STAGES == 3 && nK > 1) {
-      issue(lds1);
-      vm_wait<JPW * (STAGES - 2)>();
-    } else {
-      vm_wait<0>();
-    }
-  }
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (STAGES == 3) {
-    for (int ks = 0; ks < nK; ks += 3) {
-      step(I0{}, I2{}, ks);
-      if (ks + 1 >= nK) break;
-      step(I1{}, I0{}, ks + 1);
-      if (ks + 2 >= nK) break;
-      step(I2{}, I1{}, ks + 2);
-    }
-  } else {
-    for (int ks = 0; ks < nK; ks += 2) {
-      step(I0{}, I1{}, ks);
-      if (ks + 1 >= nK) break;
-      step(I1{}, I0{}, ks + 1);
-    }
-  }
-  // partial tile -> ws[((split*nsub + sub)*Cout + co)*cols_max + col]
-  float* W = ws + ((size_t)split * A.nsub + sub) * (size_t)A.Cout * cols_max;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4 * WN; ++j) {
-      const int col = col0 + wb * WN * 64 + j * 16 + (lane & 15);
-      if (col >= cols) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int co = co0 + wa * 64 + i * 16 + g * 4 + r;
-        if (co < A.Cout) W[(size_t)co * cols_max + col] = acc[i][j][r];
-      }
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// k_wgrad2: k_wgrad_lds's product (same tiles, same panels, same fragment reads, same partial
-// layout) with a lean issue path for the common geometry: one sub-problem, stride 1, dy on the
-// input grid (same-size convs: every 3x3 d-conv and 1x1 of the network), W in {32, 64, 128},
-// images a multiple of the 64-pixel step, Cin and the dy channel slice 64-aligned.  Then the
-// pixel offset of a lane's row in dy and x is LINEAR in the pixel index: the per-step offset is
-// one scalar (p * ld * 2) added by the buffer unit; per lane only constant row / channel /
-// tap offsets are kept, and a tap's row validity is wave-uniform per step (a 64-pixel step is
-// one image row at W 64, half a row at W 128, two rows at W 32 whose halves are waves 0-3 and
-// 4-7), its column validity a per-lane constant (W 128: one of two).  k_wgrad_lds, profiled on
-// the 256->256 3x3 at 128x128 (bs 32), spent 1.4 VALU + 1.0 SALU per MFMA on per-step pixel
-// arithmetic and ran the MFMA pipe 34% busy.
-// Stride 2 (round 6; the input grid twice the output grid): a lane's x pixel is (S (gy + rh) + ty,
-// S gx + tx) -- per lane (S rh + ty) IW + S gx + tx, per step the image and row (n IH + S gy) IW
-// (+ S 64 for the second half of a W 128 row).  That covers the stride-2 convs and, with x and dy
-// exchanged, the ConvTranspose2d(3, s2, p1, op1) weight gradient: dW[ci][co][ky][kx] = sum_g
-// x[g][ci] dy[2 g + (ky, kx) - 1][co] is the weight gradient of the stride-2 conv over dy whose
-// output gradient is x (geometry.convT_dgrad's plan; the engine's _wgrad).
-// ------------------------------------------------------------------------------------
-template <int NA, int NB, int STAGES, int WN>
-__global__ void __launch_bounds__(512) k_wgrad2(const zp_wgrad_args A, float* __restrict__ ws, int pix_per_split,
-                                                int col_tiles, int tiles_per_sub, int cols_max, const wg_bounds WB) {
-  constexpr int KP = 64;
-  static_assert(NA * NB == 8 * WN, "8 waves of 64 x (64 WN)");
-  constexpr int NBW = NB / WN;
-  constexpr int NP = NA + NB;   // panels per stage; wave w fills rows 8w..8w+7 of every panel
-  constexpr int PB = KP * 128;  // panel bytes
-  constexpr int SB = NP * PB;   // stage bytes
-  static_assert(SB * STAGES <= 160 * 1024, "LDS");
-  __shared__ uint4 lds[STAGES * SB / 16];
-
-  // XCD-aware order (bijective for any total): each XCD walks a contiguous run of (split, tile),
-  // tiles fastest, so the tiles of one split (same dy / x pixel rows) share an L2
-  const int total = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, pos = bid >> 3, q8 = total >> 3, r8 = total & 7;
-  const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + pos;
-  const int tile = lin % tiles_per_sub;
-  const int split = lin / tiles_per_sub;  // one sub-problem
-  const auto& S = A.sub[0];
-  const int cols = S.ntaps * A.Cin;
-  const int ct = tile % col_tiles, cot = tile / col_tiles;
-  const int col0 = ct * 64 * NB, co0 = cot * 64 * NA;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wa = wid / NBW, wb = wid % NBW;
-  const int W = A.GW, GHW = A.GH * A.GW;
-  const int M = A.N * GHW;
-  const int pbeg = split * pix_per_split;
-  const int pend = min(M, pbeg + pix_per_split);
-  const int nK = pend > pbeg ? (pend - pbeg) / KP : 0;
-
-  const int R = wid * 8 + (lane >> 3);  // this lane's pixel row within a step
-  const int lchunk = (lane & 7) ^ wg_swz(R);
-  const int cout8 = (A.Cout + 7) & ~7;
-  const int rh = W == 32 ? (wid >> 2) : 0;  // image-row offset of this wave's rows (wave-uniform)
-  const int gxl = W == 32 ? (R & 31) : R;   // column (W 128: + 64 * xh)
-  const int SS = A.sy;                      // input stride (1, or 2 with IH = 2 GH, IW = 2 GW)
-  // per panel: lane offsets (dy: row + channel; x: row + tap + channel, with column validity folded
-  // in as an out-of-range offset), tap row of x panels (wave-uniform)
-  unsigned vdy[NA];
-  int vx[NB];                // x: row + tap + channel offset (bytes; may be negative, the step adds p)
-  bool okx0[NB], okx1[NB];   // column validity (W 128: column half 0 / 1)
-  int tyP[NB];
-#pragma unroll
-  for (int P = 0; P < NA; ++P) {
-    const int ch = co0 + 64 * P + 8 * lchunk;
-    vdy[P] = ch < cout8 ? (unsigned)((R * S.lddy + S.cdy0 + ch) * 2) : 0x80000000u;
-  }
-#pragma unroll
-  for (int P = 0; P < NB; ++P) {
-    const int col = col0 + 64 * P + 8 * lchunk;
-    const bool ok = col < cols;
-    const int t = ok ? col / A.Cin : 0;
-    const int ci = col - t * A.Cin;
-    const int ty = S.ty[t], tx = S.tx[t];
-    tyP[P] = __builtin_amdgcn_readfirstlane(S.ty[(col0 + 64 * P) / A.Cin < S.ntaps ? (col0 + 64 * P) / A.Cin : 0]);
-    vx[P] = ((SS * rh + ty) * A.IW + SS * gxl + tx) * A.ldx * 2 + (A.cx0 + ci) * 2;
-    okx0[P] = ok && (unsigned)(SS * gxl + tx) < (unsigned)A.IW;
-    okx1[P] = ok && (unsigned)(SS * (gxl + 64) + tx) < (unsigned)A.IW;
-  }
-#if defined(__HIP_DEVICE_COMPILE__)
-  const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)A.x, (short)0, (int)WB.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc((void*)S.dy, (short)0, (int)WB.dy_bytes[0], 0x00020000);
-#endif
-  // scalar walk: pixel p of the next step to issue, its image row gy and (W 128) column half xh
-  int p_is = pbeg;
-  int gy_is, xh_is, n_is = pbeg / GHW;
-  {
-    const int r = pbeg % GHW;
-    gy_is = r / W;
-    xh_is = W == 128 ? (r / 64) & 1 : 0;
-  }
-  const int ldy2 = S.lddy * 2, ldx2 = A.ldx * 2;
-  auto issue = [&](auto slot_c) {
-    constexpr int SL = decltype(slot_c)::value;
-    const int sdy = p_is * ldy2;
-    const int sx = ((n_is * A.IH + SS * gy_is) * A.IW + SS * 64 * xh_is) * ldx2;  // (S 1: p_is * ldx2)
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-    for (int P = 0; P < NA; ++P) {
-      auto* d = (__attribute__((address_space(3))) void*)((unsigned char*)lds + SL * SB + P * PB + wid * 1024);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(drsrc, d, 16, vdy[P], sdy, 0, 0);
-    }
-#pragma unroll
-    for (int P = 0; P < NB; ++P) {
-      // the full (non-negative when valid) offset in the VGPR: a lane offset below zero is never
-      // handed to the buffer unit, whatever its range check does with the scalar part
-      const bool rowok = (unsigned)(SS * (gy_is + rh) + tyP[P]) < (unsigned)A.IH;  // wave-uniform
-      const bool ok = rowok && (xh_is ? okx1[P] : okx0[P]);
-      const unsigned v = ok ? (unsigned)(vx[P] + sx) : 0x80000000u;
-      auto* d = (__attribute__((address_space(3))) void*)((unsigned char*)lds + SL * SB + (NA + P) * PB + wid * 1024);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, d, 16, v, 0, 0, 0);
-    }
-#endif
-    // advance one 64-pixel step (images are whole steps: GHW % 64 == 0)
-    p_is += KP;
-    if (W == 128) {
-      xh_is ^= 1;
-      if (xh_is == 0) ++gy_is;
-    } else {
-      gy_is += KP / W;
-    }
-    if (gy_is >= A.GH) {
-      gy_is = 0;
-      ++n_is;
-    }
-  };
-
-  f32x4 acc[4][4 * WN];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4 * WN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int g = lane >> 4, q4 = (lane >> 2) & 3, p4 = lane & 3;
-  const int sh = (((q4 >> 1) & 1) | ((g & 1) << 1));
-  const unsigned l0 = lds_addr(lds);
-  unsigned pa[STAGES][4], pb[STAGES][4];  // per ring slot (slot offsets exceed the ds immediate)
-#pragma unroll
-  for (int sl = 0; sl < STAGES; ++sl)
-#pragma unroll
-    for (int ii = 0; ii < 4; ++ii) {
-      pa[sl][ii] = l0 + (unsigned)(sl * SB + wa * PB) + (unsigned)(128 * (8 * g + q4) + 8 * p4 + 32 * (ii ^ sh));
-      pb[sl][ii] = pa[sl][ii] + (unsigned)((NA + wb * WN - wa) * PB);
-    }
-  auto step = [&](auto cur_c, auto nxt_c, int ks) {
-    constexpr int CUR = decltype(cur_c)::value;
-    const bool more = ks + (STAGES - 1) < nK;
-    if constexpr (ZP_ABL != 1) {
-      if (more) issue(nxt_c);
-    }
-    static_for<KP / 32>([&](auto s2) {
-      uint4 af[4], bfr[4 * WN];
-      static_for<4>([&](auto ii) {
-        const uint2 a0 = ds_read_tr8<s2 * 4096>(pa[CUR][ii]);
-        const uint2 a1 = ds_read_tr8<s2 * 4096 + 512>(pa[CUR][ii]);
-        af[ii] = make_uint4(a0.x, a0.y, a1.x, a1.y);
-        static_for<WN>([&](auto w) {
-          const uint2 b0 = ds_read_tr8<w * PB + s2 * 4096>(pb[CUR][ii]);
-          const uint2 b1 = ds_read_tr8<w * PB + s2 * 4096 + 512>(pb[CUR][ii]);
-          bfr[w * 4 + ii] = make_uint4(b0.x, b0.y, b1.x, b1.y);
-        });
-      });
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-      if constexpr (ZP_ABL != 2) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4 * WN; ++j) MfmaTraits<bf16_t>::mma(acc[i][j], af[i], bfr[j]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i][0][0] += __uint_as_float(af[i].x ^ bfr[i].y);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(0);
-    });
-    if (more) vm_wait<NP * (STAGES - 2)>();
-    else vm_wait<0>();
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-  if (nK > 0) {
-    issue(I0{});
-    if (STAGES == 3 && nK > 1) {
-      issue(I1{});
-      vm_wait<NP * (STAGES - 2)>();
-    } else {
-      vm_wait<0>();
-    }
-  }
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (STAGES == 3) {
-    for (int ks = 0; ks < nK; ks += 3) {
-      step(I0{}, I2{}, ks);
-      if (ks + 1 >= nK) break;
-      step(I1{}, I0{}, ks + 1);
-      if (ks + 2 >= nK) break;
-      step(I2{}, I1{}, ks + 2);
-    }
-  } else {
-    for (int ks = 0; ks < nK; ks += 2) {
-      step(I0{}, I1{}, ks);
-      if (ks + 1 >= nK) break;
-      step(I1{}, I0{}, ks + 1);
-    }
-  }
-  float* Wp = ws + (size_t)split * (size_t)A.Cout * cols_max;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4 * WN; ++j) {
-      const int col = col0 + wb * WN * 64 + j * 16 + (lane & 15);
-      if (col >= cols) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int co = co0 + wa * 64 + i * 16 + g * 4 + r;
-        if (co < A.Cout) Wp[(size_t)co * cols_max + col] = acc[i][j][r];
-      }
-    }
-}
-
-// ws (summed over splits) -> dw in the weight's own layout.  Per element the splits are summed into
-// 8 partial sums (split k into q[k % 8] for the whole batches of 8, the rest into q[0]), combined as
-// ((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7)): fixed order, deterministic.  (Round 5) up to 32
-// splits' loads are issued before their adds (the same adds in the same order as batches of 8; one
-// batch of 8 in flight left the launch bound by 3-4 dependent memory round trips per thread), and
-// the element index is 32-bit.
-__global__ void __launch_bounds__(256) k_wgrad_reduce(const zp_wgrad_args A, const float* __restrict__ ws, int splits,
-                                                      int cols_max) {
-  const int sub = blockIdx.y;
-  const auto& S = A.sub[sub];
-  const unsigned cols = (unsigned)(S.ntaps * A.Cin);
-  const unsigned total = (unsigned)A.Cout * cols;
-  const size_t stride = (size_t)A.nsub * A.Cout * cols_max;
-  for (unsigned e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-    const unsigned co = e / cols, col = e - co * cols;
-    const int t = (int)(col / (unsigned)A.Cin), ci = (int)col - t * A.Cin;
-    const int ky = S.ky[t], kx = S.kx[t];
-    if (ci >= A.Cw || ky < 0) continue;  // padded input channels / padding taps
-    const float* p = ws + ((size_t)sub * A.Cout + co) * cols_max + col;
-    float q[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int k = 0;
-    for (; k + 32 <= splits; k += 32) {
-      float v[32];
-#pragma unroll
-      for (int u = 0; u < 32; ++u) v[u] = p[(size_t)(k + u) * stride];
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int u = 0; u < 8; ++u) q[u] += v[8 * b + u];
-    }
-    if (k + 16 <= splits) {
-      float v[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) v[u] = p[(size_t)(k + u) * stride];
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int u = 0; u < 8; ++u) q[u] += v[8 * b + u];
-      k += 16;
-    }
-    if (k + 8 <= splits) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(k + u) * stride];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) q[u] += v[u];
-      k += 8;
-    }
-    {
-      float v[7];  // the remaining < 8 splits, loaded together, added to q[0] in split order
-#pragma unroll
-      for (int u = 0; u < 7; ++u) v[u] = k + u < splits ? p[(size_t)(k + u) * stride] : 0.f;
-#pragma unroll
-      for (int u = 0; u < 7; ++u)
-        if (k + u < splits) q[0] += v[u];
-    }
-    const float s = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
-    size_t idx = A.transposed_w ? (((size_t)ci * A.Cout + co) * A.kh + ky) * A.kw + kx
-                                : (((size_t)co * A.Cw + ci) * A.kh + ky) * A.kw + kx;
-    if (A.accumulate) A.dw[idx] += s;
-    else A.dw[idx] = s;
-  }
-}
-
 }  // namespace zp
 
 using namespace zp;
 
 // ------------------------------------------------------------------------------------ host
-static int conv_flags();
-
-template <typename T, int WC, int NWP, int STAGES, bool SMALLC>
-static void launch_conv(const zp_conv_args& a, const conv_taps& tg, int gx, int gy, hipStream_t st) {
-  hipLaunchKernelGGL((k_conv<T, WC, 4, NWP, STAGES, SMALLC>), dim3(gx, gy, a.nsub), dim3(128 * NWP), 0, st,
-                     a, tg, conv_flags());
-}
-// 256 x 256 tile (bf16 only): 64 KB per LDS stage, so a 2-deep ring
-template <typename T>
-static void launch_conv_tc256(const zp_conv_args& a, const conv_taps& tg, int gx, int gy, hipStream_t st) {
-  if constexpr (sizeof(T) == 2) launch_conv<T, 8, 4, 2, false>(a, tg, gx, gy, st);
-}
-
 // Tuning overrides for sweeps (read once): ZP_CONV_TP=128|256 forces the pixel tile,
 // ZP_CONV_STAGES=2|3 forces the LDS ring depth, ZP_CONV_TC256=0 disables the 256-channel tile.
 // 0 = heuristic.
-static int env_int(const char* name) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : 0;
-}
 static bool conv_tc256_enabled() {
   static const bool v = getenv("ZP_CONV_TC256") ? env_int("ZP_CONV_TC256") != 0 : true;
   return v;
-}
-// runtime tuning knobs (zp_conv_tuning): minimum workgroup count for the 256-channel tile
-static int g_tc256_min_blocks = 1024;
-
-// cout tile: 256 (the whole layer: activations are staged once per pixel tile instead of once per
-// 128-channel tile, and 64 MFMAs per wave per LDS step instead of 32) for bf16 layers with
-// Cout % 256 == 0; else 128 / 64 / 32.
-// Measured (R34 bs 32, profiles/r01_conv_sweep.md): a win when the launch still has >= 1024
-// workgroups of 256 pixels (64x64 / 128x128 layers, the 64x64 transposed-conv phases: 1.1-1.2x),
-// a loss on 32x32 layers (128 workgroups for 256 CUs), on the 32x32 transposed-conv phases (512
-// workgroups: 78.7 us vs 70.7 us on the 128-channel tile) and on the ASPP launch, whose four
-// sub-problems (1 vs 9 taps) are too unbalanced for 512 large tiles.
-static bool strip_eligible(const zp_conv_args& a, strip_geo* sg);
-static bool quad_plan(const zp_conv_args& a, quad_geo* qg);
-static int g_quad_min_blocks = 256;  // zp_conv_tuning key 6: fewest workgroups k_conv_quad runs with
-static int g_strip_c64 = 1;  // zp_conv_tuning key 2: 64-channel layers on the strip kernel (TC 64; 27.5 -> 22.2 us at 64x64)
-// strip tile width: 128 channels, or 64 when 128-channel tiles would leave part of the 256 CUs
-// idle (128 -> 128 at 32x32, bs 32: 128 workgroups; 24.2 -> 22.7 us).  64-channel layers stay on
-// k_conv's 128-pixel tiles (27.5 us there vs 29.2 us as a 64-channel strip).
-static int strip_tc(const zp_conv_args& a) {
-  static const int en64 = getenv("ZP_STRIP_TC64") ? env_int("ZP_STRIP_TC64") : 1;
-  if (a.Cout <= 64) return 64;
-  if (!en64) return 128;
-  const long tiles = (long)a.N * a.GH * a.GW / 256;
-  if (tiles * ((a.Cout + 127) / 128) < 256) return 64;
-  return 128;
-}
-static int conv_tc(const zp_conv_args& a) {
-  if (a.dtype == ZP_F32X3 || a.dtype == ZP_F32H2) return conv3_tc(a);  // k_conv3 / k_conv3s
-  if (quad_plan(a, nullptr)) return 64;  // k_conv_quad: 64 channels x 4 phases
-  // strip-eligible layers take k_conv_strip's 128-channel tile: it stages fewer bytes per FLOP than
-  // the 256-channel k_conv tile, and a 256-channel strip tile does not fit the register file
-  // (35 spilled VGPRs)
-  if (strip_eligible(a, nullptr)) return strip_tc(a);
-  if (a.dtype != ZP_F32 && a.Cout % 256 == 0 && a.Cin >= 64 && conv_tc256_enabled()) {
-    const long M = (long)a.N * a.GH * a.GW;
-    int tmin = ZP_MAX_TAPS, tmax = 0;
-    for (int s = 0; s < a.nsub; ++s) {
-      tmin = a.sub[s].ntaps < tmin ? a.sub[s].ntaps : tmin;
-      tmax = a.sub[s].ntaps > tmax ? a.sub[s].ntaps : tmax;
-    }
-    if (ceil_div(M, 256) * (long)a.nsub >= g_tc256_min_blocks && tmax <= 4 * tmin) return 256;
-  }
-  return a.Cout > 64 ? 128 : (a.Cout > 32 ? 64 : 32);
 }
 static int conv_tp_override() {
   static const int v = env_int("ZP_CONV_TP");
@@ -2727,6 +1849,11 @@ static int conv_stages_override() {
   static const int v = env_int("ZP_CONV_STAGES");
   return v;
 }
+// runtime tuning knobs (zp_conv_tuning)
+static int g_tc256_min_blocks = 1024;  // key 0: minimum workgroup count for the 256-channel tile
+static int g_conv_flags = -1;          // key 1 (runtime A/B in one process); -1 = env / default
+static int g_strip_c64 = 1;  // key 2: 64-channel layers on the strip kernel (TC 64; 27.5 -> 22.2 us at 64x64)
+static int g_quad_min_blocks = 256;    // key 6: fewest workgroups k_conv_quad runs with
 
 // conv schedule switches: bit 1 XCD-aware tile order, bit 2 s_setprio(1) around the MFMA
 // cluster, bit 3 ping-pong (staggered wave groups), bit 4 tap-row trimming (tap rows that read only
@@ -2736,19 +1863,29 @@ static int conv_stages_override() {
 // next strip's DMA between the MFMAs of a group's first step (DM 2).  Default (measured, profiles/r01_conv_sweep.md,
 // profiles/r02_conv_ab.md): XCD order + setprio + ping-pong + trimming + k_conv_strip2 (94).
 // ZP_CONV_FLAGS / zp_conv_tuning(1, .) override for sweeps.
-static int g_conv_flags = -1;  // zp_conv_tuning key 1 (runtime A/B in one process); -1 = env / default
 static int conv_flags() {
   static const int v = getenv("ZP_CONV_FLAGS") ? env_int("ZP_CONV_FLAGS") : 94 + 128 + 256;
   return g_conv_flags >= 0 ? g_conv_flags : v;
 }
 
-// 3x3 stride-1 same-size bf16 convs on full-width tiles (W 32 / 64 / 128) whose strip of
+// k_conv1x1n's geometry (ZP_CONV1X1N=0 turns it off)
+static bool conv1x1n_ok(const zp_conv_args& a) {
+  static const int en1n = getenv("ZP_CONV1X1N") ? env_int("ZP_CONV1X1N") : 1;
+  const zp_conv_sub& S = a.sub[0];
+  return en1n && (a.dtype == ZP_BF16 || a.dtype == ZP_F16) && a.nsub == 1 && S.ntaps == 1 && S.ty[0] == 0 &&
+         S.tx[0] == 0 && (a.Cin == 32 || a.Cin == 64) && a.Cout % 64 == 0 && a.Cout / 16 <= C1N_MAXCB &&
+         a.w_rows >= a.Cout && a.k_pad >= a.Cin && !a.stats && !a.bnr_part && !a.res && !a.relu &&
+         a.out_mode == ZP_OUT_NHWC && !S.scale && !S.shift && S.ldy % 8 == 0 && S.cy0 % 8 == 0 && a.ldx % 8 == 0 &&
+         a.cx0 % 8 == 0 && a.sy == 1 && a.sx == 1 && a.GH == a.IH && a.GW == a.IW && S.OH == a.GH && S.OW == a.GW &&
+         S.oys == 1 && S.oxs == 1 && S.oyo == 0 && S.oxo == 0 && (long)a.N * a.GH * a.GW >= 65536;
+}
+
+// 3x3 stride-1 same-size 16-bit convs on full-width tiles (W 32 / 64 / 128) whose strip of
 // TR x (W + 2 pad) pixels fits the 320-row LDS slot run k_conv_strip (256-pixel tiles).
 // ZP_CONV_STRIP=0 disables.
 static bool strip_eligible(const zp_conv_args& a, strip_geo* sg) {
   static const int en = getenv("ZP_CONV_STRIP") ? env_int("ZP_CONV_STRIP") : 1;
-  if (!en || a.dtype == ZP_F32 || a.dtype == ZP_F32X3 || a.dtype == ZP_F32H2 || a.nsub != 1 || a.Cin % 64 != 0 || a.Cout % 64 != 0)
-    return false;
+  if (!en || a.dtype == ZP_F32 || a.nsub != 1 || a.Cin % 64 != 0 || a.Cout % 64 != 0) return false;
   if (a.Cout <= 64 && !g_strip_c64) return false;
   if (a.sy != 1 || a.sx != 1 || a.GH != a.IH || a.GW != a.IW) return false;
   const zp_conv_sub& S = a.sub[0];
@@ -2767,19 +1904,28 @@ static bool strip_eligible(const zp_conv_args& a, strip_geo* sg) {
   }
   const int TR = 256 / W, SW = W + 2 * pad, SR = TR * SW;
   if (SR > 320) return false;
-  if (sg) {
-    sg->W = W;
-    sg->TR = TR;
-    sg->SW = SW;
-    sg->SR = SR;
-    sg->SPW = 5;
-    sg->ty0 = ty0;
-    sg->dty = dty;
-    sg->tx0 = tx0;
-    sg->dtx = dtx;
-    sg->pad = pad;
-  }
+  sg->W = W;
+  sg->TR = TR;
+  sg->SW = SW;
+  sg->SR = SR;
+  sg->SPW = 5;
+  sg->ty0 = ty0;
+  sg->dty = dty;
+  sg->tx0 = tx0;
+  sg->dtx = dtx;
+  sg->pad = pad;
   return true;
+}
+// strip tile width: 128 channels, or 64 when 128-channel tiles would leave part of the 256 CUs
+// idle (128 -> 128 at 32x32, bs 32: 128 workgroups; 24.2 -> 22.7 us).  A 256-channel strip tile does
+// not fit the register file (35 spilled VGPRs).
+static int strip_tc(const zp_conv_args& a) {
+  static const int en64 = getenv("ZP_STRIP_TC64") ? env_int("ZP_STRIP_TC64") : 1;
+  if (a.Cout <= 64) return 64;
+  if (!en64) return 128;
+  const long tiles = (long)a.N * a.GH * a.GW / 256;
+  if (tiles * ((a.Cout + 127) / 128) < 256) return 64;
+  return 128;
 }
 
 // k_conv_quad eligibility: 16-bit, the four phases (py, px) = (0,0), (0,1), (1,0), (1,1) of a
@@ -2788,7 +1934,7 @@ static bool strip_eligible(const zp_conv_args& a, strip_geo* sg) {
 // enough workgroups to cover the CUs.  qg: the byte offset of each schedule slot's tap.
 static bool quad_plan(const zp_conv_args& a, quad_geo* qg) {
   if (!(conv_flags() & 128)) return false;
-  if (a.dtype == ZP_F32 || a.dtype == ZP_F32X3 || a.dtype == ZP_F32H2 || a.nsub != 4 || a.Cin % 64 != 0 || a.Cout % 64 != 0) return false;
+  if (a.dtype == ZP_F32 || a.nsub != 4 || a.Cin % 64 != 0 || a.Cout % 64 != 0) return false;
   if (a.sy != 1 || a.sx != 1 || a.GH != a.IH || a.GW != a.IW) return false;
   if (a.GW != 32 && a.GW != 64) return false;
   if (((long)a.GH * a.GW) % 256 != 0) return false;
@@ -2809,63 +1955,162 @@ static bool quad_plan(const zp_conv_args& a, quad_geo* qg) {
     while (t < S.ntaps && !(S.ty[t] == shift[k][0] && S.tx[t] == shift[k][1])) ++t;
     if (t == S.ntaps || (used[ph] >> t) & 1) return false;
     used[ph] |= 1 << t;
-    if (qg) qg->koff[k] = t * a.Cin * 2;
+    qg->koff[k] = t * a.Cin * 2;
   }
   return true;
 }
 
+// One launch's configuration: what zp_conv2d runs and what every query answers.
+enum conv_kind { CONV_SPLIT, CONV_C1X1N, CONV_STRIP, CONV_STRIP2, CONV_QUAD, CONV_TILE };
+struct conv_plan {
+  conv_kind kind;
+  int variant;         // zp_conv2d_config's label of the kernel (include/zp.h)
+  int tc, tp, stages;  // cout tile, pixel tile, LDS ring depth
+  bool smallc;         // k_conv's small-Cin form (Cin below one K step)
+  int gx, gy, gz;      // grid of every kind but CONV_C1X1N (gx is zp_conv2d_grid's answer for all)
+  int blocks;          // CONV_C1X1N: its persistent workgroups
+  int stat_parts, bnr_parts;
+  int dm;              // CONV_STRIP2: k_conv_strip2's DM
+  bool ms;             // CONV_QUAD: k_conv_quad's MS
+  int ncb;             // CONV_C1X1N: k_conv1x1n's NCB
+  strip_geo sg;        // CONV_STRIP, CONV_STRIP2 (x_bytes / w_bytes: the launch fills them)
+  quad_geo qg;         // CONV_QUAD (the same)
+};
+
+// k_conv's tile (CONV_TILE; CONV_C1X1N reports it too).
+// cout tile: 256 (the whole layer: activations are staged once per pixel tile instead of once per
+// 128-channel tile, and 64 MFMAs per wave per LDS step instead of 32) for bf16 layers with
+// Cout % 256 == 0; else 128 / 64 / 32.
+// Measured (R34 bs 32, profiles/r01_conv_sweep.md): a win when the launch still has >= 1024
+// workgroups of 256 pixels (64x64 / 128x128 layers, the 64x64 transposed-conv phases: 1.1-1.2x),
+// a loss on 32x32 layers (128 workgroups for 256 CUs), on the 32x32 transposed-conv phases (512
+// workgroups: 78.7 us vs 70.7 us on the 128-channel tile) and on the ASPP launch, whose four
+// sub-problems (1 vs 9 taps) are too unbalanced for 512 large tiles.
 // pixel tile: 256 (8 waves) whenever the cout tile allows it.  Measured on MI355X (R34 bs32,
 // profiles/r01_conv_sweep.md): the 8-wave 3-stage tile beats the 4-wave tiles even on the
 // 32x32 layers where it leaves part of the chip idle (fewer workgroups, but 2x the MFMA work
 // per LDS byte and deeper prefetch)
-static int conv_tp(const zp_conv_args& a) {
-  if (a.dtype == ZP_F32X3 || a.dtype == ZP_F32H2) return conv3_tp(a, conv3_tc(a));
-  int tc = a.Cout > 64 ? 128 : (a.Cout > 32 ? 64 : 32);
-  if (tc == 32) return 128;  // 32 + 256 rows do not split over 8 waves in 8-row groups
-  if (strip_eligible(a, nullptr) || quad_plan(a, nullptr)) return 256;
-  if (conv_tc(a) == 256) return 256;  // the 256-channel tile exists only with 256-pixel tiles
+static void plan_tile(const zp_conv_args& a, conv_plan& p) {
+  const long M = (long)a.N * a.GH * a.GW;
+  p.tc = a.Cout > 64 ? 128 : (a.Cout > 32 ? 64 : 32);
+  if (a.dtype != ZP_F32 && a.Cout % 256 == 0 && a.Cin >= 64 && conv_tc256_enabled()) {
+    int tmin = ZP_MAX_TAPS, tmax = 0;
+    for (int s = 0; s < a.nsub; ++s) {
+      tmin = a.sub[s].ntaps < tmin ? a.sub[s].ntaps : tmin;
+      tmax = a.sub[s].ntaps > tmax ? a.sub[s].ntaps : tmax;
+    }
+    if (ceil_div(M, 256) * (long)a.nsub >= g_tc256_min_blocks && tmax <= 4 * tmin) p.tc = 256;
+  }
   const int ov = conv_tp_override();
-  if (ov == 128 || ov == 256) return ov;
   // Cout <= 128 (one cout tile): 128-pixel tiles double the workgroup count of the 32x32 / 64x64
   // layers (tools/conv_micro.py: 128->128 @32x32 36 -> 24 us, 64->64 @64x64 28.6 -> 26.3 us);
   // the small-Cin stem keeps 256
   const int E = a.dtype == ZP_F32 ? 4 : 8;
-  if (a.Cout <= 128 && a.Cin >= 8 * E) return 128;
-  return 256;
+  if (p.tc == 32) p.tp = 128;  // 32 + 256 rows do not split over 8 waves in 8-row groups
+  else if (p.tc == 256) p.tp = 256;  // the 256-channel tile exists only with 256-pixel tiles
+  else if (ov == 128 || ov == 256) p.tp = ov;
+  else p.tp = a.Cout <= 128 && a.Cin >= 8 * E ? 128 : 256;
 }
 
-// LDS ring depth: 3, except for the two launches with very few or gather-bound K steps, where the
-// 2-deep ring's smaller LDS footprint (more resident workgroups) wins (R34 bs 32, layer report):
-// the small-Cin stem (7x7, per-lane tap gather: 100 -> 75 us) and the 32-channel-tile head
-// (1x1 320 -> 17 at 128x128, 5 K steps, HBM-bound: 99 -> 90 us).  Every other k_conv launch loses
-// with 2 stages (ASPP 217 -> 329 us).
-static int conv_stages(const zp_conv_args& a, int tc) {
+// The order of precedence: narrow-K 1x1, strip, quad, k_conv's tile (split dtypes: zp_conv3*.hip's own).
+static conv_plan plan_conv(const zp_conv_args& a) {
+  conv_plan p{};
+  const long M = (long)a.N * a.GH * a.GW;
+  const int fl = conv_flags();
+  p.smallc = a.Cin < (a.dtype == ZP_F32 ? 32 : 64);
+  if (a.dtype == ZP_F32X3 || a.dtype == ZP_F32H2) {
+    p.kind = CONV_SPLIT;  // k_conv3 / k_conv3s / k_conv3w
+    p.tc = conv3_tc(a);
+    p.tp = conv3_tp(a, p.tc);
+    p.variant = p.tc == 256 ? 6 : conv3_nsplit(a) == 1 && conv3_strip_ok(a, p.tc) ? 5 : 4;
+  } else if (conv1x1n_ok(a)) {
+    p.kind = CONV_C1X1N;
+    p.variant = 7;
+    plan_tile(a, p);
+    p.ncb = a.Cout / 16;
+    const long want = ((M + 15) / 16 + 3) / 4;  // four 16-pixel groups per workgroup and pass
+    p.blocks = (int)(want < 2L * num_cus() ? want : 2L * num_cus());  // (~200 VGPRs: 2 blocks per CU)
+  } else if (strip_eligible(a, &p.sg)) {
+    // k_conv_strip2 (lean main loop) or k_conv_strip; flags & 32: strip DMA spread over the group
+    p.kind = (fl & 64) ? CONV_STRIP2 : CONV_STRIP;
+    p.variant = (fl & 64) ? 2 : 1;
+    p.tc = strip_tc(a);
+    p.tp = 256;
+    p.dm = (fl & 256) ? 2 : (fl & 32) ? 1 : 0;
+  } else if (quad_plan(a, &p.qg)) {
+    p.kind = CONV_QUAD;  // 64 channels x 4 phases
+    p.variant = 3;
+    p.tc = 64;
+    p.tp = 256;
+    p.ms = (fl & 256) != 0;
+  } else {
+    p.kind = CONV_TILE;
+    plan_tile(a, p);
+  }
+  // LDS ring depth: 3, except for the two launches with very few or gather-bound K steps, where the
+  // 2-deep ring's smaller LDS footprint (more resident workgroups) wins (R34 bs 32, layer report):
+  // the small-Cin stem (7x7, per-lane tap gather: 100 -> 75 us) and the 32-channel-tile head
+  // (1x1 320 -> 17 at 128x128, 5 K steps, HBM-bound: 99 -> 90 us).  Every other k_conv launch loses
+  // with 2 stages (ASPP 217 -> 329 us).  The 256 x 256 tile: 64 KB per LDS stage, so a 2-deep ring.
   const int ov = conv_stages_override();
-  if (ov == 2 || ov == 3) return ov;
-  const int ke = a.dtype == ZP_F32 ? 32 : 64;  // elements per K step
-  if (a.Cin < ke || tc <= 32) return 2;
-  return 3;
+  p.stages = p.tc == 256 ? 2 : (ov == 2 || ov == 3) ? ov : (p.smallc || p.tc <= 32) ? 2 : 3;
+  p.gx = ceil_div(M, p.tp);  // (strip, quad: whole 256-pixel tiles)
+  p.gy = ceil_div(a.Cout, p.tc);
+  p.gz = p.kind == CONV_STRIP || p.kind == CONV_STRIP2 || p.kind == CONV_QUAD ? 1 : a.nsub;
+  // statistics parts: k_conv_strip2, k_conv_quad and k_conv merge their wave halves in LDS -- one
+  // part per tile and sub (k_conv_quad's tiles hold the four phases); k_conv_strip and the split
+  // forms keep one per wave half.  bnr_parts == stat_parts by construction: every kernel that takes
+  // the fused BN backward reduce (bnr_part) emits its parts exactly as it emits the statistics.
+  p.stat_parts = p.kind == CONV_SPLIT   ? (p.tp / 64) * p.gx * a.nsub
+                 : p.kind == CONV_STRIP ? 4 * p.gx
+                 : p.kind == CONV_QUAD  ? 4 * p.gx
+                                        : p.gx * p.gz;
+  p.bnr_parts = p.stat_parts;
+  return p;
 }
 
-extern "C" int zp_conv2d_stat_parts(const zp_conv_args* a);
+extern "C" int zp_conv2d_grid(const zp_conv_args* a) { return a ? plan_conv(*a).gx : 0; }
+extern "C" int zp_conv2d_stat_parts(const zp_conv_args* a) { return a ? plan_conv(*a).stat_parts : 0; }
+extern "C" int zp_conv2d_bnr_parts(const zp_conv_args* a) { return a ? plan_conv(*a).bnr_parts : 0; }
 
-// k_conv1x1n's geometry (ZP_CONV1X1N=0 turns it off)
-static int num_cus();
-static bool conv1x1n_ok(const zp_conv_args& a) {
-  static const int en1n = getenv("ZP_CONV1X1N") ? env_int("ZP_CONV1X1N") : 1;
-  const zp_conv_sub& S = a.sub[0];
-  return en1n && (a.dtype == ZP_BF16 || a.dtype == ZP_F16) && a.nsub == 1 && S.ntaps == 1 && S.ty[0] == 0 &&
-         S.tx[0] == 0 && (a.Cin == 32 || a.Cin == 64) && a.Cout % 64 == 0 && a.Cout / 16 <= C1N_MAXCB &&
-         a.w_rows >= a.Cout && a.k_pad >= a.Cin && !a.stats && !a.bnr_part && !a.res && !a.relu &&
-         a.out_mode == ZP_OUT_NHWC && !S.scale && !S.shift && S.ldy % 8 == 0 && S.cy0 % 8 == 0 && a.ldx % 8 == 0 &&
-         a.cx0 % 8 == 0 && a.sy == 1 && a.sx == 1 && a.GH == a.IH && a.GW == a.IW && S.OH == a.GH && S.OW == a.GW &&
-         S.oys == 1 && S.oxs == 1 && S.oyo == 0 && S.oxo == 0 && (long)a.N * a.GH * a.GW >= 65536;
+/* launch configuration zp_conv2d picks for these args (for kernel labels in reports) */
+extern "C" int zp_conv2d_config(const zp_conv_args* a, int* tc, int* tp, int* stages, int* variant) {
+  ZP_CHECK_ARG(a && tc && tp && stages && variant, "zp_conv2d_config: null args");
+  const conv_plan p = plan_conv(*a);
+  *tc = p.tc;
+  *tp = p.tp;
+  *stages = p.stages;
+  *variant = p.variant;
+  return ZP_OK;
 }
 
-extern "C" int zp_conv2d_grid(const zp_conv_args* a) {
-  if (!a) return 0;
-  long M = (long)a->N * a->GH * a->GW;
-  return ceil_div(M, conv_tp(*a));
+template <typename T, int WC, int NWP, int STAGES>
+static void launch_conv_st(const zp_conv_args& a, const conv_taps& tg, const conv_plan& p, hipStream_t st) {
+  const dim3 grid(p.gx, p.gy, p.gz);
+  if (p.smallc)
+    hipLaunchKernelGGL((k_conv<T, WC, 4, NWP, STAGES, true>), grid, dim3(128 * NWP), 0, st, a, tg, conv_flags());
+  else
+    hipLaunchKernelGGL((k_conv<T, WC, 4, NWP, STAGES, false>), grid, dim3(128 * NWP), 0, st, a, tg, conv_flags());
+}
+template <typename T, int WC, int NWP>
+static void launch_conv_nwp(const zp_conv_args& a, const conv_taps& tg, const conv_plan& p, hipStream_t st) {
+  if (p.stages == 3) launch_conv_st<T, WC, NWP, 3>(a, tg, p, st);
+  else launch_conv_st<T, WC, NWP, 2>(a, tg, p, st);
+}
+template <typename T>
+static void launch_conv(const zp_conv_args& a, const conv_taps& tg, const conv_plan& p, hipStream_t st) {
+  const int nwp = p.tp / 64;
+  if (p.tc == 256) {  // (16-bit only)
+    if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((k_conv<T, 8, 4, 4, 2, false>), dim3(p.gx, p.gy, p.gz), dim3(512), 0, st, a, tg, conv_flags());
+  } else if (p.tc == 128) {
+    if (nwp == 4) launch_conv_nwp<T, 4, 4>(a, tg, p, st);
+    else launch_conv_nwp<T, 4, 2>(a, tg, p, st);
+  } else if (p.tc == 64) {
+    if (nwp == 4) launch_conv_nwp<T, 2, 4>(a, tg, p, st);
+    else launch_conv_nwp<T, 2, 2>(a, tg, p, st);
+  } else {
+    launch_conv_nwp<T, 1, 2>(a, tg, p, st);
+  }
 }
 
 extern "C" int zp_conv2d(const zp_conv_args* ap, void* stream) {
@@ -2881,14 +2126,16 @@ extern "C" int zp_conv2d(const zp_conv_args* ap, void* stream) {
                                 !a.res && !a.relu && a.out_mode == ZP_OUT_NHWC && a.Cout % 4 == 0),
                "zp_conv2d: bnr_* (fused BN backward reduce) needs a plain f32 / bf16 NHWC store (no stats, "
                "residual, ReLU), bnr_x and bnr_save, Cout %% 4 == 0");
-  if (a.dtype == ZP_F32X3 || a.dtype == ZP_F32H2) return conv3_launch(a, (hipStream_t)stream, conv_flags());
+  hipStream_t st = (hipStream_t)stream;
+  const int fl = conv_flags();
+  if (a.dtype == ZP_F32X3 || a.dtype == ZP_F32H2) return conv3_launch(a, st, fl);  // (plans itself: zp_conv3.hip)
+  conv_plan p = plan_conv(a);
   const int E = a.dtype == ZP_F32 ? 4 : 8, KE = 8 * E;
-  const bool smallc = a.Cin < KE;
-  ZP_CHECK_ARG(a.Cin > 0 && a.Cin % E == 0 && (smallc || a.Cin % KE == 0),
+  ZP_CHECK_ARG(a.Cin > 0 && a.Cin % E == 0 && (p.smallc || a.Cin % KE == 0),
                "zp_conv2d: Cin %d must be a multiple of %d (or < %d and a multiple of %d)", a.Cin, KE, KE, E);
   ZP_CHECK_ARG(a.ldx >= a.cx0 + a.Cin && a.cx0 % E == 0 && a.ldx % E == 0, "zp_conv2d: bad ldx/cx0");
   ZP_CHECK_ARG(a.k_pad % KE == 0, "zp_conv2d: k_pad %d not a multiple of %d", a.k_pad, KE);
-  ZP_CHECK_ARG(a.w_rows % conv_tc(a) == 0 && a.w_rows >= a.Cout, "zp_conv2d: w_rows %d", a.w_rows);
+  ZP_CHECK_ARG(a.w_rows % p.tc == 0 && a.w_rows >= a.Cout, "zp_conv2d: w_rows %d", a.w_rows);
   ZP_CHECK_ARG((a.out_mode >= 0 && a.out_mode <= 2) || ((a.out_mode == ZP_OUT_NHWC_X3 || a.out_mode == ZP_OUT_NHWC_H2) && a.dtype == ZP_F32 && !a.stats),
                "zp_conv2d: out_mode %d", a.out_mode);
   ZP_CHECK_ARG(!(a.stats || a.bnr_part) || (!a.res && !a.relu && a.out_mode != ZP_OUT_HEAD_NCHW && !a.sub[0].scale &&
@@ -2899,7 +2146,7 @@ extern "C" int zp_conv2d(const zp_conv_args* ap, void* stream) {
     ZP_CHECK_ARG(S.w && S.y, "zp_conv2d: sub %d null w/y", s);
     ZP_CHECK_ARG(!a.bnr_part || (!S.scale && !S.shift), "zp_conv2d: bnr_* with a scale / shift epilogue");
     ZP_CHECK_ARG(S.ntaps >= 1 && S.ntaps <= ZP_MAX_TAPS, "zp_conv2d: ntaps %d", S.ntaps);
-    if (smallc) {
+    if (p.smallc) {
       ZP_CHECK_ARG(S.kw > 0 && (long)S.ntaps * a.Cin <= a.k_pad, "zp_conv2d: small-Cin taps/k_pad");
     } else {
       ZP_CHECK_ARG((long)S.ntaps * a.Cin <= a.k_pad, "zp_conv2d: k_pad %d < ntaps*Cin", a.k_pad);
@@ -2932,373 +2179,86 @@ extern "C" int zp_conv2d(const zp_conv_args* ap, void* stream) {
       tg.tx0[s] = S.tx[0];
       tg.dty[s] = ny > 1 ? S.ty[nx] - S.ty[0] : 0;
       tg.dtx[s] = nx > 1 ? S.tx[1] - S.tx[0] : 0;
-      if (smallc) continue;  // the small-Cin path decodes (kw, dil, pad) per lane instead
+      if (p.smallc) continue;  // the small-Cin path decodes (kw, dil, pad) per lane instead
       bool grid = ny * nx == S.ntaps && ny <= 32 && nx <= 32;
       for (int t = 0; grid && t < S.ntaps; ++t)
         grid = S.ty[t] == tg.ty0[s] + (t / nx) * tg.dty[s] && S.tx[t] == tg.tx0[s] + (t % nx) * tg.dtx[s];
       ZP_CHECK_ARG(grid, "zp_conv2d: sub %d taps must form a (row x column) grid of at most 32 x 32, rows outer", s);
     }
   }
-  // narrow-K 1x1 convs with a wide output (k_conv1x1n: the head's data gradient in training)
-  {
-    if (conv1x1n_ok(a)) {
-      const long groups = ((long)a.N * a.GH * a.GW + 15) / 16;
-      const long want = (groups + 3) / 4;
-      const int blocks = (int)(want < 2L * num_cus() ? want : 2L * num_cus());  // (~200 VGPRs: 2 blocks per CU)
-#define ZP_C1N(NCB)                                                                                           \
-  case NCB:                                                                                                   \
-    if (a.dtype == ZP_F16) hipLaunchKernelGGL((k_conv1x1n<f16_t, NCB>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a); \
-    else hipLaunchKernelGGL((k_conv1x1n<bf16_t, NCB>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);    \
+  p.sg.x_bytes = p.qg.x_bytes = tg.x_bytes;
+  p.sg.w_bytes = p.qg.w_bytes = tg.w_bytes[0];
+  const dim3 grid(p.gx, p.gy, p.gz);
+  const bool f16 = a.dtype == ZP_F16;
+  switch (p.kind) {
+    case CONV_C1X1N: {  // narrow-K 1x1 convs with a wide output (the head's data gradient in training)
+#define ZP_C1N(NCB)                                                                                 \
+  case NCB:                                                                                         \
+    if (f16) hipLaunchKernelGGL((k_conv1x1n<f16_t, NCB>), dim3(p.blocks), dim3(256), 0, st, a);     \
+    else hipLaunchKernelGGL((k_conv1x1n<bf16_t, NCB>), dim3(p.blocks), dim3(256), 0, st, a);        \
     break;
-      switch (a.Cout / 16) { ZP_C1N(4) ZP_C1N(8) ZP_C1N(12) ZP_C1N(16) ZP_C1N(20) ZP_C1N(24) }
+      switch (p.ncb) { ZP_C1N(4) ZP_C1N(8) ZP_C1N(12) ZP_C1N(16) ZP_C1N(20) ZP_C1N(24) }
 #undef ZP_C1N
       ZP_LAUNCH_CHECK("zp_conv2d 1x1 narrow-K");
       return ZP_OK;
     }
-  }
-  // tiny-M 1x1 convs (the ASPP image-pool conv): one wave per (grid point, 16 output channels)
-  {
-    const long mpix = (long)a.N * a.GH * a.GW;
-    const zp_conv_sub& S = a.sub[0];
-    if (E == 8 && !smallc && mpix <= 64 && a.nsub == 1 && S.ntaps == 1 && !a.stats && !a.bnr_part && !a.res &&
-        a.out_mode == ZP_OUT_NHWC && a.w_rows >= ((a.Cout + 63) / 64) * 64 && (conv_flags() & 1024) != 0) {
-      const dim3 grid((a.Cout + 63) / 64, (unsigned)mpix);
-      if (a.dtype == ZP_F16) hipLaunchKernelGGL(k_conv_smallm<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL(k_conv_smallm<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, a);
-      ZP_LAUNCH_CHECK("zp_conv2d small-M");
-      return ZP_OK;
-    }
-  }
-  const int tc = conv_tc(a);
-  const int gx = zp_conv2d_grid(&a), gy = ceil_div(a.Cout, tc);
-  hipStream_t st = (hipStream_t)stream;
-  strip_geo sg{};
-  if (tc <= 128 && strip_eligible(a, &sg)) {
-    sg.x_bytes = tg.x_bytes;
-    sg.w_bytes = tg.w_bytes[0];
-    const int sgx = (int)(((long)a.N * a.GH * a.GW) / 256);
-    const dim3 grid(sgx, gy, 1);
-    const int fl0 = conv_flags();
-    // train-mode statistics: the caller sized the partials buffer with zp_conv2d_stat_parts; the
-    // launch must emit exactly that many parts (NWP = 4 wave-halves per 256-pixel tile)
-    ZP_CHECK_ARG(!a.bnr_part || (fl0 & 64) || 4 * sgx == zp_conv2d_stat_parts(&a), "zp_conv2d: strip bnr parts");
-    ZP_CHECK_ARG(!a.stats || ((fl0 & 64) ? 1 : 4) * sgx == zp_conv2d_stat_parts(&a),
-                 "zp_conv2d: strip launch emits %d stat parts, zp_conv2d_stat_parts says %d", 4 * sgx,
-                 zp_conv2d_stat_parts(&a));
-    const int fl = conv_flags();
-    if (fl & 64) {  // k_conv_strip2 (lean main loop); flags & 32: strip DMA spread over the group
+    case CONV_STRIP2: {
       const zp_head_args H0{};
-#define ZP_STRIP2(T, WC)                                                                               \
-  if (fl & 256) hipLaunchKernelGGL((k_conv_strip2<T, WC, 5, 2>), grid, dim3(512), 0, st, a, sg, fl, H0); \
-  else if (fl & 32) hipLaunchKernelGGL((k_conv_strip2<T, WC, 5, 1>), grid, dim3(512), 0, st, a, sg, fl, H0); \
-  else hipLaunchKernelGGL((k_conv_strip2<T, WC, 5, 0>), grid, dim3(512), 0, st, a, sg, fl, H0);
-#define ZP_STRIP2B(T, WC)                                                                              \
-  if (fl & 256) hipLaunchKernelGGL((k_conv_strip2<T, WC, 5, 2, false, true>), grid, dim3(512), 0, st, a, sg, fl, H0); \
-  else if (fl & 32) hipLaunchKernelGGL((k_conv_strip2<T, WC, 5, 1, false, true>), grid, dim3(512), 0, st, a, sg, fl, H0); \
-  else hipLaunchKernelGGL((k_conv_strip2<T, WC, 5, 0, false, true>), grid, dim3(512), 0, st, a, sg, fl, H0);
+#define ZP_STRIP2(T, WC, BNR)                                                                                       \
+  if (p.dm == 2) hipLaunchKernelGGL((k_conv_strip2<T, WC, 5, 2, false, BNR>), grid, dim3(512), 0, st, a, p.sg, fl, H0);      \
+  else if (p.dm == 1) hipLaunchKernelGGL((k_conv_strip2<T, WC, 5, 1, false, BNR>), grid, dim3(512), 0, st, a, p.sg, fl, H0); \
+  else hipLaunchKernelGGL((k_conv_strip2<T, WC, 5, 0, false, BNR>), grid, dim3(512), 0, st, a, p.sg, fl, H0);
       if (a.bnr_part) {  // (bf16 only: zp_conv2d's bnr check)
-        if (tc == 64) { ZP_STRIP2B(bf16_t, 2) } else { ZP_STRIP2B(bf16_t, 4) }
-      } else if (a.dtype == ZP_F16) {
-        if (tc == 64) { ZP_STRIP2(f16_t, 2) } else { ZP_STRIP2(f16_t, 4) }
+        if (p.tc == 64) { ZP_STRIP2(bf16_t, 2, true) } else { ZP_STRIP2(bf16_t, 4, true) }
+      } else if (f16) {
+        if (p.tc == 64) { ZP_STRIP2(f16_t, 2, false) } else { ZP_STRIP2(f16_t, 4, false) }
       } else {
-        if (tc == 64) { ZP_STRIP2(bf16_t, 2) } else { ZP_STRIP2(bf16_t, 4) }
+        if (p.tc == 64) { ZP_STRIP2(bf16_t, 2, false) } else { ZP_STRIP2(bf16_t, 4, false) }
       }
 #undef ZP_STRIP2
-#undef ZP_STRIP2B
-    } else if (a.dtype == ZP_F16) {
-      if (tc == 64) hipLaunchKernelGGL((k_conv_strip<f16_t, 2, 3, 5>), grid, dim3(512), 0, st, a, sg, fl);
-      else hipLaunchKernelGGL((k_conv_strip<f16_t, 4, 3, 5>), grid, dim3(512), 0, st, a, sg, fl);
-    } else {
-      if (tc == 64) hipLaunchKernelGGL((k_conv_strip<bf16_t, 2, 3, 5>), grid, dim3(512), 0, st, a, sg, fl);
-      else hipLaunchKernelGGL((k_conv_strip<bf16_t, 4, 3, 5>), grid, dim3(512), 0, st, a, sg, fl);
+      ZP_LAUNCH_CHECK("zp_conv2d strip");
+      return ZP_OK;
     }
-    ZP_LAUNCH_CHECK("zp_conv2d strip");
-    return ZP_OK;
-  }
-  quad_geo qg{};
-  if (quad_plan(a, &qg)) {
-    qg.x_bytes = tg.x_bytes;
-    qg.w_bytes = tg.w_bytes[0];
-    const int qgx = (int)(((long)a.N * a.GH * a.GW) / 256);
-    const dim3 grid(qgx, gy, 1);
-    ZP_CHECK_ARG(!(a.stats || a.bnr_part) || 4 * qgx == zp_conv2d_stat_parts(&a),
-                 "zp_conv2d: quad launch emits %d stat parts, zp_conv2d_stat_parts says %d", 4 * qgx,
-                 zp_conv2d_stat_parts(&a));
-    const int fl = conv_flags();
-#define ZP_QUAD(T)                                                                             \
-  if (a.GW == 32 && (fl & 256)) hipLaunchKernelGGL((k_conv_quad<T, 32, true>), grid, dim3(512), 0, st, a, qg, fl); \
-  else if (a.GW == 32) hipLaunchKernelGGL((k_conv_quad<T, 32, false>), grid, dim3(512), 0, st, a, qg, fl); \
-  else if (fl & 256) hipLaunchKernelGGL((k_conv_quad<T, 64, true>), grid, dim3(512), 0, st, a, qg, fl); \
-  else hipLaunchKernelGGL((k_conv_quad<T, 64, false>), grid, dim3(512), 0, st, a, qg, fl);
-    if (a.dtype == ZP_F16) { ZP_QUAD(f16_t) } else { ZP_QUAD(bf16_t) }
+    case CONV_STRIP:
+      if (f16) {
+        if (p.tc == 64) hipLaunchKernelGGL((k_conv_strip<f16_t, 2, 3, 5>), grid, dim3(512), 0, st, a, p.sg, fl);
+        else hipLaunchKernelGGL((k_conv_strip<f16_t, 4, 3, 5>), grid, dim3(512), 0, st, a, p.sg, fl);
+      } else {
+        if (p.tc == 64) hipLaunchKernelGGL((k_conv_strip<bf16_t, 2, 3, 5>), grid, dim3(512), 0, st, a, p.sg, fl);
+        else hipLaunchKernelGGL((k_conv_strip<bf16_t, 4, 3, 5>), grid, dim3(512), 0, st, a, p.sg, fl);
+      }
+      ZP_LAUNCH_CHECK("zp_conv2d strip");
+      return ZP_OK;
+    case CONV_QUAD:
+#define ZP_QUAD(T)                                                                                              \
+  if (a.GW == 32 && p.ms) hipLaunchKernelGGL((k_conv_quad<T, 32, true>), grid, dim3(512), 0, st, a, p.qg, fl);  \
+  else if (a.GW == 32) hipLaunchKernelGGL((k_conv_quad<T, 32, false>), grid, dim3(512), 0, st, a, p.qg, fl);    \
+  else if (p.ms) hipLaunchKernelGGL((k_conv_quad<T, 64, true>), grid, dim3(512), 0, st, a, p.qg, fl);           \
+  else hipLaunchKernelGGL((k_conv_quad<T, 64, false>), grid, dim3(512), 0, st, a, p.qg, fl);
+      if (f16) { ZP_QUAD(f16_t) } else { ZP_QUAD(bf16_t) }
 #undef ZP_QUAD
-    ZP_LAUNCH_CHECK("zp_conv2d quad");
-    return ZP_OK;
+      ZP_LAUNCH_CHECK("zp_conv2d quad");
+      return ZP_OK;
+    default:  // CONV_TILE
+      if (a.dtype == ZP_BF16) launch_conv<bf16_t>(a, tg, p, st);
+      else if (f16) launch_conv<f16_t>(a, tg, p, st);
+      else launch_conv<float>(a, tg, p, st);
+      ZP_LAUNCH_CHECK("zp_conv2d");
+      return ZP_OK;
   }
-  const int nwp = conv_tp(a) / 64;
-  const int stages = conv_stages(a, tc);
-  {
-    ZP_CHECK_ARG(!(a.stats || a.bnr_part) || gx * a.nsub == zp_conv2d_stat_parts(&a),
-                 "zp_conv2d: launch emits %d stat parts, zp_conv2d_stat_parts says %d", gx * a.nsub,
-                 zp_conv2d_stat_parts(&a));
-  }
-#define ZP_DISPATCH_ST(T, WC, NWP, ST)                                   \
-  if (smallc) launch_conv<T, WC, NWP, ST, true>(a, tg, gx, gy, st);      \
-  else launch_conv<T, WC, NWP, ST, false>(a, tg, gx, gy, st);
-#define ZP_DISPATCH_NWP(T, WC, NWP)                                      \
-  if (stages == 3) { ZP_DISPATCH_ST(T, WC, NWP, 3) } else { ZP_DISPATCH_ST(T, WC, NWP, 2) }
-#define ZP_DISPATCH(T)                                                   \
-  if (tc == 256) {                                                       \
-    launch_conv_tc256<T>(a, tg, gx, gy, st);                             \
-  } else if (tc == 128) {                                                \
-    if (nwp == 4) { ZP_DISPATCH_NWP(T, 4, 4) } else { ZP_DISPATCH_NWP(T, 4, 2) } \
-  } else if (tc == 64) {                                                 \
-    if (nwp == 4) { ZP_DISPATCH_NWP(T, 2, 4) } else { ZP_DISPATCH_NWP(T, 2, 2) } \
-  } else {                                                               \
-    ZP_DISPATCH_NWP(T, 1, 2)                                             \
-  }
-  if (a.dtype == ZP_BF16) {
-    ZP_DISPATCH(bf16_t)
-  } else if (a.dtype == ZP_F16) {
-    ZP_DISPATCH(f16_t)
-  } else {
-    ZP_DISPATCH(float)
-  }
-#undef ZP_DISPATCH_ST
-#undef ZP_DISPATCH_NWP
-#undef ZP_DISPATCH
-  ZP_LAUNCH_CHECK("zp_conv2d");
-  return ZP_OK;
-}
-
-static void wgrad_plan(const zp_wgrad_args& a, int* splits, int* col_tiles, int* cols_max, int* pix_per) {
-  long M = (long)a.N * a.GH * a.GW;
-  int cm = 0;
-  for (int s = 0; s < a.nsub; ++s) cm = cm > a.sub[s].ntaps * a.Cin ? cm : a.sub[s].ntaps * a.Cin;
-  int ct = ceil_div(cm, WG_TILE);
-  int tiles = ct * ceil_div(a.Cout, WG_TILE) * a.nsub;
-  const int KP = a.dtype == ZP_BF16 ? 32 : 16;
-  // aim for >= 1024 workgroups, but keep >= 8 K steps per split
-  long sp = (1024 + tiles - 1) / tiles;
-  long maxsp = M / (8 * KP);
-  if (maxsp < 1) maxsp = 1;
-  if (sp > maxsp) sp = maxsp;
-  if (sp > 256) sp = 256;
-  long pp = (M + sp - 1) / sp;
-  pp = (pp + KP - 1) / KP * KP;
-  sp = (M + pp - 1) / pp;
-  *splits = (int)sp;
-  *col_tiles = ct;
-  *cols_max = cm;
-  *pix_per = (int)pp;
-}
-
-// bf16: the LDS-DMA kernel (k_wgrad_lds).  Tile 128 co x 256 col (3 stages), or 64 x 512 (2 stages)
-// when Cout <= 64; KP 64.  One workgroup per CU (144 KB LDS): aim for ~2 workgroups per CU
-// over the launch, each with >= 16 K steps.  ZP_WGRAD=0 selects the register-staged k_wgrad.
-static bool wgrad_lds(const zp_wgrad_args& a) {
-  static const int v = getenv("ZP_WGRAD") ? env_int("ZP_WGRAD") : 1;
-  return a.dtype == ZP_BF16 && v != 0;
-}
-// tile: 0 = 64 co x 512 col (Cout <= 64), 1 = 128 x 256, 2 = 256 x 256 (Cout >= 256: fewer staged
-// bytes per FLOP -- the L2 -> LDS stream, not the MFMA, bounds this kernel).  Round 5: a k_wgrad2
-// launch whose 256 x 256 plan would give each split under 2048 pixels takes 128 x 256 instead --
-// few tiles (a 3x3 256 -> 256 at 32 x 32 has 9) mean ~28 splits, and each split writes a 256 KB f32
-// partial slab (64 MB per launch, re-read by k_wgrad_reduce) for 1216 pixels of MFMA work:
-// measured 739 -> 679 us over layer4's 11 wgrads, the 1 x 1 convs 43 -> 32 us; the 128 x 128
-// decoder / layer5 wgrads (18724 / 4681 pixels per split) stay on 256 x 256 (1116 vs 1328 us).
-// ZP_WGRAD_BIG=0: always 128 x 256; 2: always 256 x 256 (A/B)
-static bool wgrad2_eligible(const zp_wgrad_args& a);
-static int num_cus();
-extern int g_wgrad2_rounds_v;
-static int wgrad_cfg(const zp_wgrad_args& a) {
-  static const int big = getenv("ZP_WGRAD_BIG") ? env_int("ZP_WGRAD_BIG") : 1;
-  if (a.Cout <= 64) return 0;
-  if (a.Cout < 256 || !big) return 1;
-  // (round 6) a Cout the 256-row tiles would pad by more than the 128-row ones (320: 512 against
-  // 384 rows -- the ConvT weight gradient as the stride-2 conv over dy) takes 128 x 256: measured
-  // 276 -> 261 us for up2's ConvT (tools/wgrad_ab.py, profiles/r06_conv_ablations.md)
-  if (big == 1 && (a.Cout + 255) / 256 * 256 > (a.Cout + 127) / 128 * 128) return 1;
-  if (big == 1 && wgrad2_eligible(a)) {
-    long M = (long)a.N * a.GH * a.GW;
-    int cm = 0;
-    for (int s = 0; s < a.nsub; ++s) cm = cm > a.sub[s].ntaps * a.Cin ? cm : a.sub[s].ntaps * a.Cin;
-    const long tiles = (long)ceil_div(cm, 256) * ceil_div(a.Cout, 256);
-    long sp = (long)g_wgrad2_rounds_v * num_cus() / tiles;
-    const long maxsp = M / (16 * 64) > 0 ? M / (16 * 64) : 1;
-    sp = sp < 1 ? 1 : (sp > maxsp ? maxsp : sp);
-    if (M / sp < 2048) return 1;
-  }
-  return 2;
-}
-// k_wgrad2 (lean issue path) for the common geometry -- see the kernel's header comment.
-// zp_conv_tuning key 3: 0 disables it; key 4: its workgroup rounds over the CUs (default 1: fewer,
-// longer workgroups than k_wgrad_lds's 1024 -- the split-K partial slabs are written and re-read
-// in full -- and never a partial extra round; one round measured fastest).
-static int g_wgrad2 = 1, g_wgrad2_rounds = 1, g_wgrad_lds_rounds = 1;
-int g_wgrad2_rounds_v = 1;  // (g_wgrad2_rounds, read by wgrad_cfg above)
-static int num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0)
-      n = 256;
-  }
-  return n;
-}
-static bool wgrad2_eligible(const zp_wgrad_args& a) {
-  if (!g_wgrad2 || a.dtype != ZP_BF16 || a.nsub != 1 || a.sy != a.sx || (a.sy != 1 && a.sy != 2)) return false;
-  if (a.IH != a.sy * a.GH || a.IW != a.sx * a.GW || (a.GW != 32 && a.GW != 64 && a.GW != 128)) return false;
-  if (((long)a.GH * a.GW) % 64 != 0 || a.Cin % 64 != 0) return false;
-  const auto& S = a.sub[0];
-  return S.oys == 1 && S.oxs == 1 && S.oyo == 0 && S.oxo == 0 && S.OH == a.GH && S.OW == a.GW;
-}
-static void wgrad_plan_lds(const zp_wgrad_args& a, int* splits, int* col_tiles, int* cols_max, int* pix_per) {
-  long M = (long)a.N * a.GH * a.GW;
-  int cm = 0;
-  for (int s = 0; s < a.nsub; ++s) cm = cm > a.sub[s].ntaps * a.Cin ? cm : a.sub[s].ntaps * a.Cin;
-  const int cfg = wgrad_cfg(a);
-  const int tco = cfg == 0 ? 64 : (cfg == 1 ? 128 : 256), tcol = cfg == 0 ? 512 : 256, KP = 64;
-  int ct = ceil_div(cm, tcol);
-  int tiles = ct * ceil_div(a.Cout, tco) * a.nsub;
-  // target workgroup count: 1024 (R34 bs 32 train step 19.93 -> 19.71 ms vs 512; 2048: 19.81).
-  // ZP_WGRAD_WG overrides for sweeps (read once, so the workspace size query agrees)
-  static const int target_lds = getenv("ZP_WGRAD_WG") ? env_int("ZP_WGRAD_WG") : 1024;
-  const bool lean = wgrad2_eligible(a);
-  // k_wgrad2: workgroups (one per CU at a time: 96-144 KB of LDS) in whole rounds over the CUs --
-  // a grid one workgroup past a round costs a full extra workgroup lifetime (513 vs 512 ran 1.6x)
-  // k_wgrad_lds: the same whole-round plan when zp_conv_tuning key 5 > 0, else ~target_lds workgroups
-  long sp = lean ? (long)g_wgrad2_rounds * num_cus() / tiles
-                 : g_wgrad_lds_rounds > 0 ? (long)g_wgrad_lds_rounds * num_cus() / tiles
-                                          : (target_lds + tiles - 1) / tiles;
-  if (sp < 1) sp = 1;
-  long maxsp = M / (16 * KP);
-  if (maxsp < 1) maxsp = 1;
-  if (sp > maxsp) sp = maxsp;
-  if (sp > 256) sp = 256;
-  long pp = (M + sp - 1) / sp;
-  pp = (pp + KP - 1) / KP * KP;
-  sp = (M + pp - 1) / pp;  // never more than requested: pp only grew
-  // k_wgrad_lds: pad the split count so the launch is a multiple of 8 workgroups (its XCD-aware
-  // order needs it); padding splits have an empty pixel range and write zero partials
-  if (!lean && g_wgrad_lds_rounds <= 0)
-    while ((sp * tiles) % 8) ++sp;
-  *splits = (int)sp;
-  *col_tiles = ct;
-  *cols_max = cm;
-  *pix_per = (int)pp;
-}
-
-extern "C" long long zp_conv2d_wgrad_ws_bytes(const zp_wgrad_args* a) {
-  if (!a || a->nsub < 1 || a->nsub > ZP_MAX_SUB) return -1;
-  int sp, ct, cm, pp;
-  if (wgrad_lds(*a)) wgrad_plan_lds(*a, &sp, &ct, &cm, &pp);
-  else wgrad_plan(*a, &sp, &ct, &cm, &pp);
-  return (long long)sp * a->nsub * a->Cout * (long long)cm * 4;
-}
-
-extern "C" int zp_conv2d_wgrad(const zp_wgrad_args* ap, void* ws, void* stream) {
-  ZP_CHECK_ARG(ap && ws, "zp_conv2d_wgrad: null args/workspace");
-  const zp_wgrad_args& a = *ap;
-  ZP_CHECK_ARG(a.dtype == ZP_F32 || a.dtype == ZP_BF16, "zp_conv2d_wgrad: dtype");
-  ZP_CHECK_ARG(a.nsub >= 1 && a.nsub <= ZP_MAX_SUB && a.dw && a.x, "zp_conv2d_wgrad: bad args");
-  const int E = a.dtype == ZP_BF16 ? 8 : 4;
-  ZP_CHECK_ARG(a.Cin % E == 0 && a.cx0 % E == 0 && a.ldx % E == 0, "zp_conv2d_wgrad: Cin/cx0/ldx alignment");
-  ZP_CHECK_ARG(a.Cw >= 1 && a.Cw <= a.Cin, "zp_conv2d_wgrad: Cw");
-  for (int s = 0; s < a.nsub; ++s) {
-    ZP_CHECK_ARG(a.sub[s].dy && a.sub[s].ntaps >= 1 && a.sub[s].ntaps <= ZP_MAX_TAPS, "zp_conv2d_wgrad: sub %d", s);
-    ZP_CHECK_ARG(a.sub[s].cdy0 % E == 0 && a.sub[s].lddy % E == 0 &&
-                 a.sub[s].lddy >= a.sub[s].cdy0 + ((a.Cout + E - 1) / E) * E,
-                 "zp_conv2d_wgrad: dy ld must cover Cout rounded to %d", E);
-  }
-  int sp, ct, cm, pp;
-  hipStream_t st = (hipStream_t)stream;
-  if (wgrad_lds(a)) {
-    wgrad_plan_lds(a, &sp, &ct, &cm, &pp);
-    wg_bounds wb{};
-    const long long xb = (long long)a.N * a.IH * a.IW * a.ldx * 2;
-    ZP_CHECK_ARG(xb < (1ll << 31), "zp_conv2d_wgrad: input %lld B must stay below 2 GiB (split the batch)", xb);
-    wb.x_bytes = (unsigned)xb;
-    for (int s = 0; s < a.nsub; ++s) {
-      const long long db = (long long)a.N * a.sub[s].OH * a.sub[s].OW * a.sub[s].lddy * 2;
-      ZP_CHECK_ARG(db < (1ll << 31), "zp_conv2d_wgrad: dy %lld B must stay below 2 GiB", db);
-      wb.dy_bytes[s] = (unsigned)db;
-    }
-    const int cfg = wgrad_cfg(a);
-    if (wgrad2_eligible(a)) {
-      const int tiles = ct * ceil_div(a.Cout, cfg == 0 ? 64 : (cfg == 1 ? 128 : 256));
-      if (cfg == 0)
-        hipLaunchKernelGGL((k_wgrad2<1, 8, 2, 1>), dim3(sp * tiles), dim3(512), 0, st, a, (float*)ws, pp, ct, tiles, cm, wb);
-      else if (cfg == 1)
-        hipLaunchKernelGGL((k_wgrad2<2, 4, 3, 1>), dim3(sp * tiles), dim3(512), 0, st, a, (float*)ws, pp, ct, tiles, cm, wb);
-      else
-        hipLaunchKernelGGL((k_wgrad2<4, 4, 2, 2>), dim3(sp * tiles), dim3(512), 0, st, a, (float*)ws, pp, ct, tiles, cm, wb);
-    } else if (cfg == 0) {
-      const int tiles = ct * ceil_div(a.Cout, 64);
-      hipLaunchKernelGGL((k_wgrad_lds<64, 1, 8, 2, 1>), dim3(sp * a.nsub * tiles), dim3(512), 0, st, a, (float*)ws,
-                         pp, ct, tiles, cm, wb);
-    } else if (cfg == 1) {
-      const int tiles = ct * ceil_div(a.Cout, 128);
-      hipLaunchKernelGGL((k_wgrad_lds<64, 2, 4, 3, 1>), dim3(sp * a.nsub * tiles), dim3(512), 0, st, a, (float*)ws,
-                         pp, ct, tiles, cm, wb);
-    } else {
-      const int tiles = ct * ceil_div(a.Cout, 256);
-      hipLaunchKernelGGL((k_wgrad_lds<64, 4, 4, 2, 2>), dim3(sp * a.nsub * tiles), dim3(512), 0, st, a, (float*)ws,
-                         pp, ct, tiles, cm, wb);
-    }
-  } else {
-    wgrad_plan(a, &sp, &ct, &cm, &pp);
-    dim3 grid(sp, ct * ceil_div(a.Cout, WG_TILE), a.nsub);
-    if (a.dtype == ZP_BF16)
-      hipLaunchKernelGGL(k_wgrad<bf16_t>, grid, dim3(256), 0, st, a, (float*)ws, pp, ct, cm);
-    else
-      hipLaunchKernelGGL(k_wgrad<float>, grid, dim3(256), 0, st, a, (float*)ws, pp, ct, cm);
-  }
-  ZP_LAUNCH_CHECK("zp_conv2d_wgrad");
-  long tot = (long)a.Cout * cm;
-  int rb = (int)((tot + 255) / 256);
-  if (rb > 4096) rb = 4096;
-  hipLaunchKernelGGL(k_wgrad_reduce, dim3(rb, a.nsub), dim3(256), 0, st, a, (const float*)ws, sp, cm);
-  ZP_LAUNCH_CHECK("zp_conv2d_wgrad reduce");
-  return ZP_OK;
-}
-
-extern "C" int zp_conv2d_stat_parts(const zp_conv_args* a) {
-  if (!a) return 0;
-  if (a->dtype == ZP_F32X3 || a->dtype == ZP_F32H2) return (conv_tp(*a) / 64) * zp_conv2d_grid(a) * a->nsub;
-  // round 5: k_conv_strip2, k_conv_quad and k_conv merge their wave halves in LDS -- one part per tile
-  // (k_conv_quad: per tile and phase); k_conv_strip (flags & 64 off) keeps one per wave half
-  if (conv_tc(*a) <= 128 && strip_eligible(*a, nullptr))
-    return (int)(((long)a->N * a->GH * a->GW) / 256) * ((conv_flags() & 64) ? 1 : 4);
-  if (quad_plan(*a, nullptr)) return 4 * (int)(((long)a->N * a->GH * a->GW) / 256);
-  return zp_conv2d_grid(a) * a->nsub;
-}
-
-extern "C" int zp_conv2d_bnr_parts(const zp_conv_args* a) {
-  if (!a) return 0;
-  // k_conv_strip2 sums its wave halves in LDS: one part per 256-pixel tile
-  if (a->dtype != ZP_F32 && conv_tc(*a) <= 128 && strip_eligible(*a, nullptr) && (conv_flags() & 64))
-    return (int)(((long)a->N * a->GH * a->GW) / 256);
-  return zp_conv2d_stat_parts(a);
 }
 
 // the 16-bit fused head: a 3x3 stride-1 conv on the 128-channel strip tile (k_conv_strip2, two cout
-// tiles for Cout 256)
-static bool head16_ok(const zp_conv_args& a) {
-  if ((a.dtype != ZP_BF16 && a.dtype != ZP_F16) || a.nsub != 1 || a.Cout != 256 || a.out_mode != ZP_OUT_NHWC ||
-      a.stats || !(conv_flags() & 64))
-    return false;
+// tiles for Cout 256); ZP_F32H2: the wide two-plane tile, unsplit
+static bool head_ok(const zp_conv_args& a, const conv_plan& p) {
+  if (a.nsub != 1 || a.Cout != 256 || a.out_mode != ZP_OUT_NHWC) return false;
+  if (a.dtype == ZP_F32H2) return p.tc == 256 && conv3w_tp_head(a) == 256 && conv3w_splitk(a) == 1;
+  if ((a.dtype != ZP_BF16 && a.dtype != ZP_F16) || a.stats) return false;
   if (a.res && (a.ldr % 8 != 0 || a.cr0 % 8 != 0)) return false;
-  return strip_eligible(a, nullptr) && conv_tc(a) == 128;
+  return p.kind == CONV_STRIP2 && p.tc == 128;
 }
 
-extern "C" int zp_conv2d_head_ok(const zp_conv_args* a) {
-  if (!a) return 0;
-  if (a->dtype == ZP_BF16 || a->dtype == ZP_F16) return head16_ok(*a);
-  return a->dtype == ZP_F32H2 && a->nsub == 1 && a->Cout == 256 && a->out_mode == ZP_OUT_NHWC &&
-         conv3_tc(*a) == 256 && conv3w_tp_head(*a) == 256 && conv3w_splitk(*a) == 1;
-}
+extern "C" int zp_conv2d_head_ok(const zp_conv_args* a) { return a && head_ok(*a, plan_conv(*a)); }
 
 extern "C" long long zp_conv2d_head_ws(const zp_conv_args* a) {
   if (!a || !(a->dtype == ZP_BF16 || a->dtype == ZP_F16)) return 0;
@@ -3307,7 +2267,8 @@ extern "C" long long zp_conv2d_head_ws(const zp_conv_args* a) {
 
 extern "C" int zp_conv2d_head(const zp_conv_args* a, const zp_head_args* h, void* stream) {
   ZP_CHECK_ARG(a && h, "zp_conv2d_head: null args");
-  ZP_CHECK_ARG(zp_conv2d_head_ok(a), "zp_conv2d_head: not a fused-head geometry (zp_conv2d_head_ok)");
+  conv_plan p = plan_conv(*a);
+  ZP_CHECK_ARG(head_ok(*a, p), "zp_conv2d_head: not a fused-head geometry (zp_conv2d_head_ok)");
   if (a->dtype == ZP_F32H2) return conv3_launch(*a, (hipStream_t)stream, conv_flags(), h);
   // ZP_BF16 / ZP_F16: the strip kernel with the head epilogue, then the cout tiles' combine
   const zp_conv_args& A = *a;
@@ -3323,15 +2284,14 @@ extern "C" int zp_conv2d_head(const zp_conv_args* a, const zp_head_args* h, void
   ZP_CHECK_ARG(A.sub[0].OH == A.GH && A.sub[0].OW == A.GW, "zp_conv2d_head: output grid");
   const long long xb = (long long)A.N * A.IH * A.IW * A.ldx * 2, wb = (long long)A.w_rows * A.k_pad * 2;
   ZP_CHECK_ARG(xb < (1ll << 31) && wb < (1ll << 31), "zp_conv2d_head: input / weights must stay below 2 GiB");
-  strip_geo sg{};
-  ZP_CHECK_ARG(strip_eligible(A, &sg), "zp_conv2d_head: not a strip geometry");
-  sg.x_bytes = (unsigned)xb;
-  sg.w_bytes = (unsigned)wb;
+  ZP_CHECK_ARG(p.kind == CONV_STRIP2, "zp_conv2d_head: not a strip geometry");
+  p.sg.x_bytes = (unsigned)xb;
+  p.sg.w_bytes = (unsigned)wb;
   hipStream_t st = (hipStream_t)stream;
   const int fl = conv_flags();
-  const dim3 grid((unsigned)(((long)A.N * A.GH * A.GW) / 256), 2u, 1u);
-  if (A.dtype == ZP_F16) hipLaunchKernelGGL((k_conv_strip2<f16_t, 4, 5, 2, true>), grid, dim3(512), 0, st, A, sg, fl, *h);
-  else hipLaunchKernelGGL((k_conv_strip2<bf16_t, 4, 5, 2, true>), grid, dim3(512), 0, st, A, sg, fl, *h);
+  const dim3 grid(p.gx, p.gy, 1u);  // (two 128-channel cout tiles; always DM 2, whatever the flags say)
+  if (A.dtype == ZP_F16) hipLaunchKernelGGL((k_conv_strip2<f16_t, 4, 5, 2, true>), grid, dim3(512), 0, st, A, p.sg, fl, *h);
+  else hipLaunchKernelGGL((k_conv_strip2<bf16_t, 4, 5, 2, true>), grid, dim3(512), 0, st, A, p.sg, fl, *h);
   ZP_LAUNCH_CHECK("zp_conv2d_head (16-bit conv + head partials)");
   const int M = A.N * A.GH * A.GW;
   hipLaunchKernelGGL(k_head_combine16, dim3((M + 255) / 256), dim3(256), 0, st, h->ws, M, A.GH * A.GW, h->cout, h->bias,
@@ -3340,37 +2300,6 @@ extern "C" int zp_conv2d_head(const zp_conv_args* a, const zp_head_args* h, void
   return ZP_OK;
 }
 
-/* launch configuration zp_conv2d picks for these args (for kernel labels in reports) */
-extern "C" int zp_conv2d_config(const zp_conv_args* a, int* tc, int* tp, int* stages, int* variant) {
-  ZP_CHECK_ARG(a && tc && tp && stages && variant, "zp_conv2d_config: null args");
-  *tc = conv_tc(*a);
-  *tp = conv_tp(*a);
-  *stages = *tc == 256 ? 2 : conv_stages(*a, *tc);
-  *variant = (a->dtype == ZP_F32X3 || a->dtype == ZP_F32H2) ? (*tc == 256 ? 6 : conv3_nsplit(*a) == 1 && conv3_strip_ok(*a, *tc) ? 5 : 4) : conv1x1n_ok(*a) ? 7 : quad_plan(*a, nullptr) ? 3 : *tc <= 128 && strip_eligible(*a, nullptr) ? ((conv_flags() & 64) ? 2 : 1) : 0;
-  return ZP_OK;
-}
-
-/* runtime tuning knobs (tests / sweeps).  key 0: minimum workgroups for the 256-channel conv tile
- * (default 1024); key 1: conv schedule flags (-1 = ZP_CONV_FLAGS / default); key 2: 64-channel
- * layers on the strip kernel (default 1); key 3: k_wgrad2 (default 1); key 4: k_wgrad2's
- * workgroup rounds over the CUs (default 1); key 5: k_wgrad_lds's workgroup rounds (default 1; 0 =
- * the older ~1024-workgroup target padded to a multiple of 8); key 6: the fewest workgroups
- * k_conv_quad runs with (default 256); key 7: split-fp32 strip kernel k_conv3s (0 off, 1 the
- * 64-channel tiles, 2 also the 128-channel tiles; -1 = ZP_CONV3_STRIP / default 1); key 8: the
- * fewest workgroups a split-fp32 launch runs 128-channel tiles with (fewer: 64-channel tiles);
- * keys 10-12: the wide two-plane tile (on / fewest workgroups / split-K); key 13: its accumulation
- * form (0 flushed correction accumulator, 1 one scaled accumulator, 2 per-step partial sums, the
- * default; -1 = ZP_CONV3W_ACC); key 14: its 256 x 128 pixel tile (0 off, 1 on; -1 = ZP_CONV3W_TP128);
- * key 15: zp_bn_train_finalize's statistics merge in one launch (1, default) or two (0; -1 = ZP_BN_FUSED);
- * key 16: k_conv3's multi-sub launches (the merged ASPP) with a tile's subs adjacent on one XCD (1) or
- * the sub slowest (0, default: measured faster; -1 = ZP_CONV3_SUBINT); key 17: k_conv3w's multi-sub
- * launches (the ConvT phases) with a pixel tile's phases adjacent on one XCD (1) or phase by phase,
- * longest first (0, default: measured faster; -1 = ZP_CONV3W_SUBINT); key 18: k_conv3w's 256 x 256 tile
- * on v_mfma_f32_32x32x16_f16 (k_conv3w32; 1) or 16 x 16 x 32 (0, default; -1 = ZP_CONV3W_MF32);
- * key 19: ring depth (2, 3, 4) of k_conv3's register-pipelined two-plane 64-channel tile (-1 =
- * ZP_CONV3_PIPE_ST or 2, the default: measured fastest); key 20: persistent workgroups per CU of the two-plane stem (1 or 2; -1 = ZP_STEM_WGS or 1); key 21: the wide strip tile's next-step pixel
- * fragments read before the step's barrier (1) or after it (0; -1 = ZP_CONV3W_PFB or 1).
- * Returns the previous value. */
 /* split-fp32 split-K workspace: bytes of f32 slices zp_conv2d uses for these args when a.stats
  * points to that many (0: the launch is not split) */
 extern "C" long long zp_conv2d_split_ws(const zp_conv_args* a) {
@@ -3379,57 +2308,35 @@ extern "C" long long zp_conv2d_split_ws(const zp_conv_args* a) {
   return ns > 1 ? (long long)ns * a->nsub * a->N * a->GH * a->GW * a->Cout * 4 : 0;
 }
 
+/* runtime tuning knobs: include/zp.h lists the keys.  Returns the previous value. */
 extern "C" int zp_conv_tuning(int key, int value) {
-  if (key == 0) {
-    const int old = g_tc256_min_blocks;
-    g_tc256_min_blocks = value;
-    return old;
+  int* g = nullptr;
+  switch (key) {
+    case 0: g = &g_tc256_min_blocks; break;
+    case 1: g = &g_conv_flags; break;
+    case 2: g = &g_strip_c64; break;
+    case 6: g = &g_quad_min_blocks; break;
+    case 3:
+    case 4:
+    case 5: return wgrad_tuning(key, value);
+    case 7: return conv3_strip_mode(value);
+    case 8: return conv3_min_blocks(value);
+    case 9: return conv3_splitk_mode(value);
+    case 10: return conv3w_mode(value);
+    case 11: return conv3w_min_blocks(value);
+    case 12: return conv3w_splitk_mode(value);
+    case 13: return conv3w_acc_mode(value);
+    case 14: return conv3w_tp128_mode(value);
+    case 15: return bn_fused_mode(value);
+    case 16: return conv3_subint_mode(value);
+    case 17: return conv3w_subint_mode(value);
+    case 18: return conv3w_mf32_mode(value);
+    case 19: return conv3_pipe_st_mode(value);
+    case 20: return stem_wgs_mode(value);
+    case 21: return conv3w_pfb_mode(value);
+    default: return -1;
   }
-  if (key == 1) {
-    const int old = g_conv_flags;
-    g_conv_flags = value;
-    return old;
-  }
-  if (key == 2) {
-    const int old = g_strip_c64;
-    g_strip_c64 = value;
-    return old;
-  }
-  if (key == 3) {
-    const int old = g_wgrad2;
-    g_wgrad2 = value;
-    return old;
-  }
-  if (key == 5) {
-    const int old = g_wgrad_lds_rounds;
-    g_wgrad_lds_rounds = value >= 0 ? value : 1;
-    return old;
-  }
-  if (key == 6) {
-    const int old = g_quad_min_blocks;
-    g_quad_min_blocks = value;
-    return old;
-  }
-  if (key == 7) return conv3_strip_mode(value);
-  if (key == 8) return conv3_min_blocks(value);
-  if (key == 9) return conv3_splitk_mode(value);
-  if (key == 10) return conv3w_mode(value);
-  if (key == 11) return conv3w_min_blocks(value);
-  if (key == 12) return conv3w_splitk_mode(value);
-  if (key == 13) return conv3w_acc_mode(value);
-  if (key == 14) return conv3w_tp128_mode(value);
-  if (key == 15) return bn_fused_mode(value);
-  if (key == 16) return conv3_subint_mode(value);
-  if (key == 17) return conv3w_subint_mode(value);
-  if (key == 18) return conv3w_mf32_mode(value);
-  if (key == 19) return conv3_pipe_st_mode(value);
-  if (key == 20) return stem_wgs_mode(value);
-  if (key == 21) return conv3w_pfb_mode(value);
-  if (key == 4) {
-    const int old = g_wgrad2_rounds;
-    g_wgrad2_rounds = value > 0 ? value : 1;
-    g_wgrad2_rounds_v = g_wgrad2_rounds;
-    return old;
-  }
-  return -1;
+  const int old = *g;
+  *g = value;
+  return old;
 }

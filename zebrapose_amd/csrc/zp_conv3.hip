@@ -1099,12 +1099,6 @@ __global__ void __launch_bounds__(512) k_conv3s(const zp_conv_args A, const stri
   conv3_epilogue<NPL, WC, WP>(A, S, acc, p0, c0, wc, wp, lane, M, GHW, flags, SG.rflag);
 }
 
-
-static int env_int(const char* name) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : 0;
-}
-
 // zp_conv_tuning key 8.  256 (one workgroup per CU): layer2's 128 -> 128 3x3 at 32 x 32, bs 32
 // (128 workgroups of 128 x 256) 107 -> 75 us on 64-channel strip tiles; 512 / 1024 also move
 // layer4 / layer5 (256 / 512 workgroups) and slow them, 198 -> 248 / 715 -> 1450 us (g16 logs)

@@ -1,9 +1,18 @@
-// Device helpers shared by the conv kernels of zp_conv.hip and zp_conv3.hip (MFMA operand traits,
+// Device helpers shared by the conv kernels of zp_conv.hip, zp_wgrad.hip and zp_conv3.hip (MFMA operand traits,
 // counted vmcnt waits, LDS addressing, immediate-offset ds_read_b128, compile-time loops, DPP row
 // sums, the per-launch tap grid).
 #pragma once
 #include <type_traits>
 #include "zp_common.h"
+
+// Diagnostic ablation builds only (tools/build_ablation.sh -> libzp_abl<N>.so; wrong results):
+// ZP_ABL 1 = k_conv / k_conv_strip / k_wgrad_lds issue no LDS-DMA, 2 = they run no MFMA, 3 = k_conv
+// / k_conv_strip stage only the weights (no activation DMA), 4 = k_conv_strip stages only the strips,
+// 6 = the 16-bit NHWC epilogue stores nothing, 7 = it loads no BN scale / shift.
+// The product build is ZP_ABL 0.
+#ifndef ZP_ABL
+#define ZP_ABL 0
+#endif
 
 namespace zp {
 

@@ -663,7 +663,7 @@ class Engine:
 
     def _convT_wgrad_swap(self, unit, x: Act, dy: Act):
         """True when a ConvTranspose2d(3, s2, p1, op1) weight gradient runs as the stride-2 conv's
-        over dy with x as its output gradient (zp_conv.hip k_wgrad2, stride 2): dW[ci][co][ky][kx] =
+        over dy with x as its output gradient (zp_wgrad.hip k_wgrad2, stride 2): dW[ci][co][ky][kx] =
         sum_g x[g][ci] dy[2 g + (ky, kx) - 1][co], the ConvT weight's own [in][out][k][k] layout.
         16-bit only (the lean kernel's dtype); the four-phase form otherwise (ZP_CONVT_WGRAD_SWAP=0)."""
         return (self.convT_wgrad_swap and unit.kind == "convT" and self.dt == L.ZP_BF16
