@@ -29,6 +29,9 @@
  *   zp_decode          binary_code_helper/CNN_output_to_pose.py:34-64, 100-130 and
  *                      class_id_encoder_decoder.py:17-28 (bits -> id -> LUT -> 2D/3D)
  *   zp_lut_coarsen     binary_code_helper/generate_new_dict.py:4-33 (ignore_bit LUT)
+ *   zp_ce_loss, zp_code_digits, zp_decode_radix, zp_pack_digits
+ *                      the d-ary code ablation (config_ablation/exp_lmo_ablation_*: 'CE' loss,
+ *                      common_ops.py:21-28, class_id_encoder_decoder.py:17-28, 43-63)
  *   zp_adam            torch.optim.Adam step used by train_v6.py:268-269, 338
  */
 #ifndef ZP_H_
@@ -392,6 +395,24 @@ int zp_code_loss(const float* code_logits, const double* mask01, const float* ma
 int zp_code_loss_bwd(const float* code_logits, const double* mask01, const float* mask_logits, const void* gt,
                      int gt_f64, int B, int L, int H, int W, int mask_code, const double* coef,
                      const double* grad_scale, float* dcode, void* stream);
+/* loss_b of BinaryCodeLoss('CE', mask_binary_code_loss=mask_code, d, False) -- the d-ary code
+ * ablation (model/BinaryCodeNet.py:23-24, 47-48, 57-60, 65; config_ablation/exp_lmo_ablation_*), f64
+ * like the reference (its mask is f64, so z and the cross-entropy are):
+ *   code_logits f32 [B][L*d][H][W] (step i's d class logits are channels i*d .. i*d+d-1);
+ *   mask: as zp_code_loss (mask01's raw f64 value multiplies the logits, :48);
+ *   gt [B][L][H][W]: the digit planes, f64 if gt_f64 else u8, each in [0, d);
+ *   z[b][i*d+k][p] = (mask_code ? m[b][p] : 1) * code[b][i*d+k][p];
+ *   out f64[1] = mean over (b, i, p) of logsumexp_k z - z[gt]: masked-out pixels count, with log d.
+ * Per-block partial sums in a grid fixed by B*L*H*W, then one block in a fixed order:
+ * deterministic.  2 <= d <= 256.  ws: zp_ce_loss_ws_bytes(B, L, H, W) bytes. */
+long long zp_ce_loss_ws_bytes(int B, int L, int H, int W);
+int zp_ce_loss(const float* code_logits, const double* mask01, const float* mask_logits, const void* gt,
+               int gt_f64, int B, int L, int d, int H, int W, int mask_code, double* out, void* ws, void* stream);
+/* dcode[b][i*d+k][p] = gscale * m * (softmax_k(z) - [k == gt]) / (B*L*H*W) (m = 1 unless mask_code),
+ * computed in f64 and rounded once to f32; gscale = *grad_scale (f64 device scalar) or 1 if NULL */
+int zp_ce_loss_bwd(const float* code_logits, const double* mask01, const float* mask_logits, const void* gt,
+                   int gt_f64, int B, int L, int d, int H, int W, int mask_code, const double* grad_scale,
+                   float* dcode, void* stream);
 /* MaskLoss (BinaryCodeNet.py:89-93): out f32[1] = mean |sigmoid(x) - g| over n elements
  * (x = mask logits [B][1][H][W] viewed as [B][H][W]); ws: zp_mask_loss_ws_bytes(n) bytes */
 long long zp_mask_loss_ws_bytes(long long n);
@@ -415,6 +436,18 @@ long long zp_decode_ws_bytes(int B, int H, int W);
 int zp_decode(const float* mask_logits, const float* code_logits, int B, int H, int W, int Lfull,
               int L, const float* lut, const int* lut_index, const int* bbox, int bbox_size,
               int* ids, int* counts, int* xy, float* xyz, void* ws, void* stream);
+/* d-ary codes (common_ops.py:21-28, the 'CE' branch): digits [B][L][H][W] (u8, or f64 if out_f64)
+ * = argmax_k code_logits[b][i*d+k][p], the lowest k on a tie (np.argmax); code_logits f32
+ * [B][L*d][H][W], 2 <= d <= 256 */
+int zp_code_digits(const float* code_logits, int B, int L, int d, int H, int W, int out_f64, void* digits,
+                   void* stream);
+/* zp_decode for d-ary codes (CNN_output_to_pose.py:100-130 with class_base = d): id = sum_i
+ * digit_i * d^(L-1-i) (class_id_encoder_decoder.py:17-28) with zp_code_digits' digits over all L
+ * steps; lut f32 [n_lut][d^L][3], d^L <= 2^24.  Mask threshold, row-major compaction, truncating
+ * bbox map, NaN class -> (0, 0, 0), optional ids, lut_index and ws: as zp_decode. */
+int zp_decode_radix(const float* mask_logits, const float* code_logits, int B, int H, int W, int L, int d,
+                    const float* lut, const int* lut_index, const int* bbox, int bbox_size, int* ids,
+                    int* counts, int* xy, float* xyz, void* ws, void* stream);
 /* out[n][3] (f32) = mean over the 2^(old-new) children of lut64 (f64, summed in order) */
 int zp_lut_coarsen(const double* lut64, int old_bits, int new_bits, float* out, void* stream);
 
@@ -456,6 +489,11 @@ int zp_crop_image(const uint8_t* imgs, int n_img, int H, int W, const int* img_i
 int zp_crop_gt(const uint8_t* gts, const uint8_t* masks, const uint8_t* entire_masks, int n_img, int H, int W,
                const int* img_index, const int* bbox, int B, int S, int L, uint8_t* code, float* mask_out,
                float* entire_out, void* stream);
+/* GT digit planes of a d-ary code, d = 2^s: bits u8 [B][nbits][H][W] (zp_crop_gt's planes, channel 0 =
+ * MSB) -> digits u8 [B][nbits/s][H][W], digit_i = planes [s*i, s*i+s) read MSB first -- with nbits = 16
+ * the reference's class_id_image_to_class_code_images(id, d, 16/s, 65536)
+ * (class_id_encoder_decoder.py:43-63): digit_i = (id >> s*(L-1-i)) & (d-1).  nbits % s == 0, s <= 8 */
+int zp_pack_digits(const uint8_t* bits, int B, int nbits, int H, int W, int s, uint8_t* digits, void* stream);
 
 /* ---- optimizer ----------------------------------------------------------------------- */
 /* torch.optim.Adam (no weight decay, amsgrad off) over one flat f32 buffer; step >= 1 */

@@ -106,12 +106,17 @@ _SIGS = {
     "zp_code_loss_ws_bytes": (i64, [i32, i32, i32, i32]),
     "zp_code_loss": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "zp_code_loss_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "zp_ce_loss_ws_bytes": (i64, [i32, i32, i32, i32]),
+    "zp_ce_loss": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "zp_ce_loss_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "zp_mask_loss_ws_bytes": (i64, [i64]),
     "zp_mask_loss": (i32, [vp, vp, i64, vp, vp, vp]),
     "zp_mask_loss_bwd": (i32, [vp, vp, i64, vp, vp, vp]),
     "zp_threshold": (i32, [vp, i64, i32, vp, vp]),
     "zp_decode_ws_bytes": (i64, [i32, i32, i32]),
     "zp_decode": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "zp_code_digits": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "zp_decode_radix": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     "zp_lut_coarsen": (i32, [vp, i32, i32, vp, vp]),
     "zp_adam": (i32, [vp, vp, vp, vp, i64, f64, f64, f64, f64, i64, vp]),
     "zp_pack_weight_multi": (i32, [i32, vp, vp, i64, vp]),
@@ -123,6 +128,7 @@ _SIGS = {
     "zp_pose_error": (i32, [i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
     "zp_crop_image": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
     "zp_crop_gt": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "zp_pack_digits": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
     "zp_adam_multi": (i32, [i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, i64, vp]),
     "zp_adam_multi_dev": (i32, [i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, vp, vp]),
     "zp_split_range_flag": (i32, [vp]),

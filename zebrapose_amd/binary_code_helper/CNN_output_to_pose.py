@@ -55,20 +55,20 @@ def _fingerprint(d):
     return len(d), tuple(vals)
 
 
-def _decoder_for(dict_class_id_3D_points, device):
+def _decoder_for(dict_class_id_3D_points, device, class_base=2):
     """The cache entry keeps a strong reference to the dict, so its id() cannot be recycled by
     another object while cached; a changed size / sampled entry rebuilds the LUT.
 
     The dict is treated as immutable once loaded (as the reference's test.py uses it): an in-place
     edit of entries outside the sampled ids (_FP_IDS) that keeps the size is NOT detected.  After
     editing a loaded dict in place, call ``clear_decoder_cache()``."""
-    key = (id(dict_class_id_3D_points), str(device))
+    key = (id(dict_class_id_3D_points), str(device), int(class_base))
     fp = _fingerprint(dict_class_id_3D_points)
     hit = _DEC_CACHE.get(key)
     if hit is not None and hit[0] is dict_class_id_3D_points and hit[1] == fp:
         _DEC_CACHE.move_to_end(key)
         return hit[2]
-    dec = Decoder(_lut_from_dict(dict_class_id_3D_points), device=device)
+    dec = Decoder(_lut_from_dict(dict_class_id_3D_points), device=device, class_base=class_base)
     _DEC_CACHE[key] = (dict_class_id_3D_points, fp, dec)
     _DEC_CACHE.move_to_end(key)
     while len(_DEC_CACHE) > _DEC_CACHE_MAX:
@@ -86,10 +86,31 @@ def _bits_to_logits(bits):
     return np.where(np.asarray(bits) > 0.5, np.float32(1.0), np.float32(-1.0)).astype(np.float32)
 
 
-def decode_correspondences(mask_image, class_code_image, Bbox, Bbox_Size, dict_class_id_3D_points, device="cuda"):
-    """Device version of :110-129 for one crop: (Original_Points_2D int64 [N,2], Points_3D f32 [N,3])."""
+def _digits_to_logits(digits, d):
+    """digit planes [H, W, L] -> one-hot logits [L * d, H, W] the device argmax maps back (exact)."""
+    dg = np.asarray(digits).astype(np.int64)
+    H, W, L = dg.shape
+    if dg.min() < 0 or dg.max() >= d:
+        raise ValueError(f"code digits must lie in [0, {d})")
+    out = np.full((L, d, H, W), -1.0, dtype=np.float32)
+    li, yi, xi = np.meshgrid(np.arange(L), np.arange(H), np.arange(W), indexing="ij")
+    out[li, dg.transpose(2, 0, 1), yi, xi] = 1.0
+    return out.reshape(L * d, H, W)
+
+
+def decode_correspondences(mask_image, class_code_image, Bbox, Bbox_Size, dict_class_id_3D_points, device="cuda",
+                           class_base=2):
+    """Device version of :110-129 for one crop: (Original_Points_2D int64 [N,2], Points_3D f32 [N,3]).
+    class_base d != 2: class_code_image holds the d-ary digits [H, W, L] (zp_decode_radix)."""
     L = class_code_image.shape[2]
-    dec = _decoder_for(dict_class_id_3D_points, device)
+    dec = _decoder_for(dict_class_id_3D_points, device, class_base)
+    if class_base != 2:
+        if dec.steps != L:
+            raise ValueError(f"code image has {L} digits but the dictionary has {dec.steps} base-{class_base}")
+        m = torch.from_numpy(_bits_to_logits(mask_image)[None, None]).to(device)
+        c = torch.from_numpy(_digits_to_logits(class_code_image, int(class_base))[None]).to(device)
+        counts, xy, xyz = dec(m, c, np.asarray(Bbox).reshape(1, 4), bbox_size=Bbox_Size)
+        return Decoder.to_host(counts, xy, xyz)[0]
     if dec.bits != L:
         raise ValueError(f"code image has {L} bits but the dictionary has {dec.bits}")
     m = torch.from_numpy(_bits_to_logits(mask_image)[None, None]).to(device)
@@ -102,8 +123,6 @@ def CNN_outputs_to_object_pose(mask_image, class_code_image, Bbox, Bbox_Size, cl
                                dict_class_id_3D_points=None, intrinsic_matrix=None):
     """:100-160 -- correspondences on the device, then RANSAC-EPnP (cv2) / Progressive-X as in the
     reference.  Returns (R, t, success)."""
-    if class_base != 2:
-        raise NotImplementedError("only binary codes (class_base 2) are on the hot path")
     if intrinsic_matrix is None:
         intrinsic_matrix = np.zeros((3, 3))
         intrinsic_matrix[0, 0] = 572.4114
@@ -112,7 +131,8 @@ def CNN_outputs_to_object_pose(mask_image, class_code_image, Bbox, Bbox_Size, cl
         intrinsic_matrix[1, 2] = 242.04899
         intrinsic_matrix[2, 2] = 1.0
     success, rot, tvecs = False, [], []
-    p2d, p3d = decode_correspondences(mask_image, class_code_image, Bbox, Bbox_Size, dict_class_id_3D_points)
+    p2d, p3d = decode_correspondences(mask_image, class_code_image, Bbox, Bbox_Size, dict_class_id_3D_points,
+                                      class_base=class_base)
     if len(p2d) >= 6:
         success = True
         coord_2d = np.ascontiguousarray(p2d.astype(np.float32))

@@ -60,10 +60,27 @@ def _u8(t, name, ndim):
 class CropPipeline:
     """Batched square-ROI crops of device-resident images (``crop_square_resize`` path)."""
 
-    def __init__(self, crop_size_img=256, crop_size_gt=128, code_bits=16, padding_ratio=1.5):
+    def __init__(self, crop_size_img=256, crop_size_gt=128, code_bits=16, padding_ratio=1.5, class_base=2,
+                 iterations=None):
+        """class_base d != 2 (the d-ary code ablation): ``code`` holds the ``iterations`` digit planes
+        of class_id_image_to_class_code_images(id, d, iterations, 65536)
+        (class_id_encoder_decoder.py:43-63; iterations defaults to log_d 65536)."""
         self.S_img, self.S_gt = int(crop_size_img), int(crop_size_gt)
         self.L = int(code_bits)
         self.padding_ratio = padding_ratio
+        self.class_base = d = int(class_base)
+        self.digit_bits = 0
+        if d != 2:
+            s = d.bit_length() - 1
+            if d < 2 or d > 256 or d & (d - 1) or 16 % s:
+                raise ValueError(f"class_base {class_base}: a power of two whose power is 65536 is needed")
+            if iterations is None:
+                iterations = 16 // s
+            if d ** int(iterations) != 65536:  # class_id_encoder_decoder.py:47-48
+                raise ValueError("this combination of base and iteration is not possible")
+            self.digit_bits, self.L = s, 16
+        elif iterations is not None and int(iterations) != self.L:
+            raise ValueError("class_base 2: iterations is code_bits")
 
     def boxes(self, Bboxes, img_w, img_h):
         """Host box arithmetic for a batch of raw boxes [B, 4] -> (padded boxes int32 [B, 4] fed to
@@ -83,7 +100,7 @@ class CropPipeline:
     def __call__(self, images, img_index, boxes, gt_images=None, masks=None, entire_masks=None):
         """images u8 [N, H, W, 3] (BGR, device); img_index int [B]; boxes = padded boxes int [B, 4].
         Returns dict: x f32 [B, 3, S_img, S_img] and, when the GT inputs are given, code u8
-        [B, L, S_gt, S_gt], mask / entire_mask f32 [B, S_gt, S_gt]."""
+        [B, L, S_gt, S_gt] (bit planes, or the d-ary digits for class_base d), mask / entire_mask f32 [B, S_gt, S_gt]."""
         images = _u8(images, "images", 4)
         gt_images = _u8(gt_images, "gt_images", 4)
         masks = _u8(masks, "masks", 3)
@@ -112,5 +129,9 @@ class CropPipeline:
             e = torch.empty((B, S, S), dtype=torch.float32, device=dev) if entire_masks is not None else None
             L.call("zp_crop_gt", L.ptr(gt_images), L.ptr(masks), L.ptr(entire_masks), N, H, W, ii.data_ptr(),
                    bb.data_ptr(), B, S, self.L, L.ptr(code), L.ptr(m), L.ptr(e), st)
+            if code is not None and self.digit_bits:  # the 16 bit planes -> 16 / s digit planes (zp_pack_digits)
+                digits = torch.empty((B, 16 // self.digit_bits, S, S), dtype=torch.uint8, device=dev)
+                L.call("zp_pack_digits", code.data_ptr(), B, 16, S, S, self.digit_bits, digits.data_ptr(), st)
+                code = digits
             out.update(code=code, mask=m, entire_mask=e)
         return out

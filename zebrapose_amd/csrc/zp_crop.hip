@@ -172,6 +172,21 @@ __global__ void __launch_bounds__(256) k_crop_gt(const uint8_t* __restrict__ gts
   if (entire_out) entire_out[(size_t)b * S * S + p] = (float)((double)ev / 255.0);
 }
 
+// digit planes of a d-ary code from zp_crop_gt's 16 bit planes (d = 2^s, L = 16 / s steps):
+// class_id_image_to_class_code_images(id, d, L, 65536) (class_id_encoder_decoder.py:43-63) gives
+// digit_i = (id >> s (L - 1 - i)) & (d - 1), i.e. bit planes [s i, s i + s) of id's low 16 bits, MSB first
+__global__ void __launch_bounds__(256) k_pack_digits(const uint8_t* __restrict__ bits, int HW, int nbits, int s,
+                                                     uint8_t* __restrict__ digits) {
+  const int b = blockIdx.z, i = blockIdx.y;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= HW) return;
+  const int L = nbits / s;
+  const uint8_t* bp = bits + ((size_t)b * nbits + (size_t)i * s) * HW + p;
+  int v = 0;
+  for (int j = 0; j < s; ++j) v = (v << 1) | (bp[(size_t)j * HW] & 1);
+  digits[((size_t)b * L + i) * HW + p] = (uint8_t)v;
+}
+
 }  // namespace zp
 
 using namespace zp;
@@ -197,5 +212,17 @@ extern "C" int zp_crop_gt(const uint8_t* gts, const uint8_t* masks, const uint8_
   hipLaunchKernelGGL(k_crop_gt, dim3((S * S + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, gts, masks,
                      entire_masks, H, W, img_index, bbox, S, L, code, mask_out, entire_out);
   ZP_LAUNCH_CHECK("zp_crop_gt");
+  return ZP_OK;
+}
+
+extern "C" int zp_pack_digits(const uint8_t* bits, int B, int nbits, int H, int W, int s, uint8_t* digits, void* stream) {
+  ZP_CHECK_ARG(bits && digits && B > 0 && B <= 65535 && H > 0 && W > 0 && (long long)H * W < (1ll << 30),
+               "zp_pack_digits: bad args");
+  ZP_CHECK_ARG(s >= 1 && s <= 8 && nbits >= s && nbits <= 24 && nbits % s == 0,
+               "zp_pack_digits: %d bit planes do not split into digits of %d bits", nbits, s);
+  const int HW = H * W;
+  hipLaunchKernelGGL(k_pack_digits, dim3((HW + 255) / 256, nbits / s, B), dim3(256), 0, (hipStream_t)stream, bits, HW,
+                     nbits, s, digits);
+  ZP_LAUNCH_CHECK("zp_pack_digits");
   return ZP_OK;
 }

@@ -9,6 +9,8 @@
 //   CNN_output_to_pose.py:34-50                      x' = int(Bbox[2]/Bbox_Size * x + Bbox[0]) (f64, trunc)
 //   CNN_output_to_pose.py:128-129                    P2D/P3D cast to float32 for PnP
 //   generate_new_dict.py:4-33                        ignore_bit LUT = f64 mean of the 2^k children
+//   common_ops.py:21-28 ('CE')                       digit_i = argmax_k softmax(code[i * d .. i * d + d))_k
+//   class_id_encoder_decoder.py:17-28 (class_base d) id = sum_i digit_i * d^(L-1-i)
 //
 // Two passes over tiles of 1024 pixels: (1) ids + per-tile mask counts, (2) per-tile
 // offsets (prefix over the crop's earlier tiles) + block scan + ordered writes.
@@ -62,7 +64,8 @@ __global__ void __launch_bounds__(256) k_decode_ids(const float* __restrict__ ml
 }
 
 __global__ void __launch_bounds__(256) k_decode_emit(const int* __restrict__ packed, const int* __restrict__ tile_cnt,
-                                                     int tiles, int H, int W, int L, const float* __restrict__ lut,
+                                                     int tiles, int H, int W, size_t lut_floats,
+                                                     const float* __restrict__ lut,
                                                      const int* __restrict__ lut_index, const int* __restrict__ bbox,
                                                      int bbox_size, int* __restrict__ counts, int* __restrict__ xy,
                                                      float* __restrict__ xyz) {
@@ -101,7 +104,7 @@ __global__ void __launch_bounds__(256) k_decode_emit(const int* __restrict__ pac
   const double bx = bbox[b * 4 + 0], by = bbox[b * 4 + 1];
   const double rx = (double)bbox[b * 4 + 2] / (double)bbox_size;
   const double ry = (double)bbox[b * 4 + 3] / (double)bbox_size;
-  const float* L3 = lut + (size_t)(lut_index ? lut_index[b] : 0) * ((size_t)3 << L);
+  const float* L3 = lut + (size_t)(lut_index ? lut_index[b] : 0) * lut_floats;  // (3 floats per class id)
   int* oxy = xy + (size_t)b * HW * 2;
   float* oxyz = xyz + (size_t)b * HW * 3;
 #pragma unroll
@@ -119,6 +122,84 @@ __global__ void __launch_bounds__(256) k_decode_emit(const int* __restrict__ pac
     oxyz[3 * pos + 2] = d;
     ++pos;
   }
+}
+
+// argmax over the d class logits of step i at four consecutive pixels (planes HW apart): the first
+// maximum wins (np.argmax, common_ops.py:26), a NaN never does.  softmax is monotonic, so the argmax
+// of the logits is the argmax of the reference's probabilities wherever the top two logits differ by
+// more than the f32 softmax's rounding.
+__device__ __forceinline__ void digits4(const float* __restrict__ x, size_t HW, int d, int n, bool vec, int* dg) {
+  float best[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    best[q] = 0.f;
+    dg[q] = 0;
+  }
+  for (int k = 0; k < d; ++k) {
+    const float* xr = x + (size_t)k * HW;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (vec) {
+      const float4 t = *(const float4*)xr;
+      v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+    } else {
+      for (int q = 0; q < n; ++q) v[q] = xr[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (k == 0 || v[q] > best[q]) {
+        best[q] = v[q];
+        dg[q] = k;
+      }
+  }
+}
+
+// digit planes of d-ary code logits [B][L * d][HW] -> [B][L][HW] (u8, or f64 like the reference's
+// numpy result); one thread per (b, i, 4 pixels)
+__global__ void __launch_bounds__(256) k_code_digits(const float* __restrict__ clog, int HW, int L, int d, int out_f64,
+                                                     void* __restrict__ out) {
+  const int b = blockIdx.z, i = blockIdx.y;
+  const int p0 = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (p0 >= HW) return;
+  const int n = min(4, HW - p0);
+  const bool vec = n == 4 && (HW & 3) == 0;
+  int dg[4];
+  digits4(clog + ((size_t)(b * L + i) * d) * HW + p0, (size_t)HW, d, n, vec, dg);
+  const size_t o = (size_t)(b * L + i) * HW + p0;
+  for (int q = 0; q < n; ++q) {
+    if (out_f64) ((double*)out)[o + q] = (double)dg[q];
+    else ((uint8_t*)out)[o + q] = (uint8_t)dg[q];
+  }
+}
+
+// k_decode_ids for d-ary codes: id = sum_i digit_i * d^(L-1-i) (Horner), same packed / ids / tile counts
+__global__ void __launch_bounds__(256) k_decode_ids_radix(const float* __restrict__ mlog, const float* __restrict__ clog,
+                                                          int HW, int L, int d, int* __restrict__ packed,
+                                                          int* __restrict__ ids, int* __restrict__ tile_cnt, int tiles) {
+  const int b = blockIdx.y, tile = blockIdx.x;
+  const int p0 = tile * DEC_TILE + threadIdx.x * 4;
+  __shared__ int wsum[4];
+  int cnt = 0;
+  if (p0 < HW) {
+    const int n = min(4, HW - p0);
+    const bool vec = n == 4 && (HW & 3) == 0;
+    int id[4] = {0, 0, 0, 0};
+    for (int i = 0; i < L; ++i) {
+      int dg[4];
+      digits4(clog + ((size_t)(b * L + i) * d) * HW + p0, (size_t)HW, d, n, vec, dg);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) id[q] = id[q] * d + dg[q];
+    }
+    for (int q = 0; q < n; ++q) {
+      const int mb = mlog[(size_t)b * HW + p0 + q] > kHalfLogit;
+      packed[(size_t)b * HW + p0 + q] = mb ? id[q] : -1;
+      if (ids) ids[(size_t)b * HW + p0 + q] = id[q];
+      cnt += mb;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) tile_cnt[b * tiles + tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
 __global__ void k_lut_coarsen(const double* __restrict__ lut, int k, int n_new, float* __restrict__ out) {
@@ -160,9 +241,44 @@ extern "C" int zp_decode(const float* mask_logits, const float* code_logits, int
   hipLaunchKernelGGL(k_decode_ids, dim3(tiles, B), dim3(256), 0, st, mask_logits, code_logits, HW, Lfull, L, packed,
                      ids, tile_cnt, tiles);
   ZP_LAUNCH_CHECK("zp_decode ids");
-  hipLaunchKernelGGL(k_decode_emit, dim3(tiles, B), dim3(256), 0, st, packed, tile_cnt, tiles, H, W, L, lut, lut_index,
-                     bbox, bbox_size, counts, xy, xyz);
+  hipLaunchKernelGGL(k_decode_emit, dim3(tiles, B), dim3(256), 0, st, packed, tile_cnt, tiles, H, W, (size_t)3 << L, lut,
+                     lut_index, bbox, bbox_size, counts, xy, xyz);
   ZP_LAUNCH_CHECK("zp_decode emit");
+  return ZP_OK;
+}
+
+extern "C" int zp_code_digits(const float* code_logits, int B, int L, int d, int H, int W, int out_f64, void* digits,
+                              void* stream) {
+  ZP_CHECK_ARG(code_logits && digits, "zp_code_digits: null pointer");
+  ZP_CHECK_ARG(B > 0 && B <= 65535 && L >= 1 && L <= 65535 && d >= 2 && d <= 256 && H > 0 && W > 0 &&
+                   (long long)H * W < (1ll << 30),
+               "zp_code_digits: bad sizes");
+  const int HW = H * W;
+  hipLaunchKernelGGL(k_code_digits, dim3((HW + 1023) / 1024, L, B), dim3(256), 0, (hipStream_t)stream, code_logits, HW, L,
+                     d, out_f64, digits);
+  ZP_LAUNCH_CHECK("zp_code_digits");
+  return ZP_OK;
+}
+
+extern "C" int zp_decode_radix(const float* mask_logits, const float* code_logits, int B, int H, int W, int L, int d,
+                               const float* lut, const int* lut_index, const int* bbox, int bbox_size, int* ids,
+                               int* counts, int* xy, float* xyz, void* ws, void* stream) {
+  ZP_CHECK_ARG(mask_logits && code_logits && lut && bbox && counts && xy && xyz && ws, "zp_decode_radix: null pointer");
+  ZP_CHECK_ARG(B > 0 && H > 0 && W > 0 && L >= 1 && d >= 2 && d <= 256 && bbox_size > 0, "zp_decode_radix: bad sizes");
+  long long nid = 1;  // d^L class ids, at most 2^24 (zp_decode's limit)
+  for (int i = 0; i < L && nid <= (1ll << 24); ++i) nid *= d;
+  ZP_CHECK_ARG(nid <= (1ll << 24), "zp_decode_radix: %d steps of %d classes exceed 2^24 class ids", L, d);
+  const int HW = H * W;
+  const int tiles = (HW + DEC_TILE - 1) / DEC_TILE;
+  int* packed = (int*)ws;
+  int* tile_cnt = packed + (size_t)B * HW;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_decode_ids_radix, dim3(tiles, B), dim3(256), 0, st, mask_logits, code_logits, HW, L, d, packed, ids,
+                     tile_cnt, tiles);
+  ZP_LAUNCH_CHECK("zp_decode_radix ids");
+  hipLaunchKernelGGL(k_decode_emit, dim3(tiles, B), dim3(256), 0, st, packed, tile_cnt, tiles, H, W, (size_t)3 * nid, lut,
+                     lut_index, bbox, bbox_size, counts, xy, xyz);
+  ZP_LAUNCH_CHECK("zp_decode_radix emit");
   return ZP_OK;
 }
 

@@ -215,6 +215,84 @@ __global__ void k_mask_grad(const float* __restrict__ x, const float* __restrict
   }
 }
 
+// ---- 'CE' code loss (BinaryCodeNet.py:47-48, 57-60, 65; nn.CrossEntropyLoss(reduction="mean") over
+// pred.reshape(-1, d, H, W) against gt.view(-1, H, W).long()).  One lane per (b, i, pixel): its d class
+// logits sit HW floats apart (NCHW), so a wave's 64 lanes read 64 consecutive floats of one class
+// plane per step.  The class row is never held: one pass for the maximum, one for the sum (f64).
+__device__ __forceinline__ int ce_target(const void* gt, int gt_f64, size_t idx, int d) {
+  int t = gt_f64 ? (int)((const double*)gt)[idx] : (int)((const uint8_t*)gt)[idx];
+  return t < 0 ? 0 : (t >= d ? d - 1 : t);  // (memory safety only: the reference raises for such a digit)
+}
+
+__device__ __forceinline__ double ce_mask(const double* m01, const float* mlog, size_t e, int mask_code) {
+  if (!mask_code) return 1.0;
+  return m01 ? m01[e] : (mlog[e] > kHalf ? 1.0 : 0.0);  // :48 multiplies by the raw f64 mask
+}
+
+// log-sum-exp of z_k = m * x_k over the d planes at x (stride HW): returns max, *lse = log sum exp(z - max)
+__device__ __forceinline__ double ce_lse(const float* __restrict__ x, size_t HW, int d, double m, double* lse) {
+  double mx = m * (double)x[0];
+  for (int k = 1; k < d; ++k) mx = fmax(mx, m * (double)x[(size_t)k * HW]);
+  double s = 0;
+  for (int k = 0; k < d; ++k) s += exp(m * (double)x[(size_t)k * HW] - mx);
+  *lse = log(s);
+  return mx;
+}
+
+__global__ void __launch_bounds__(256) k_ce_partials(const float* __restrict__ clog, const double* __restrict__ m01,
+                                                     const float* __restrict__ mlog, const void* __restrict__ gt,
+                                                     int gt_f64, long N, int L, int d, int HW, int mask_code,
+                                                     double* __restrict__ part) {
+  __shared__ double sh[4];
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  double v = 0;
+  if (e < N) {  // (the tail lanes of the last block add 0)
+    const long LHW = (long)L * HW;
+    const long b = e / LHW, r = e - b * LHW;
+    const int i = (int)(r / HW), p = (int)(r - (long)i * HW);
+    const double m = ce_mask(m01, mlog, (size_t)b * HW + p, mask_code);
+    const float* x = clog + ((size_t)(b * L + i) * d) * HW + p;
+    double lse;
+    const double mx = ce_lse(x, (size_t)HW, d, m, &lse);
+    const int t = ce_target(gt, gt_f64, (size_t)e, d);
+    v = lse - (m * (double)x[(size_t)t * HW] - mx);  // -log_softmax(z)[t]
+  }
+  v = block_sum(v, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = v;
+}
+
+// one block walks the per-block partials in a fixed order (the grid above depends on N only)
+__global__ void __launch_bounds__(256) k_ce_finalize(const double* __restrict__ part, int nblk, long N,
+                                                     double* __restrict__ out) {
+  __shared__ double sh[4];
+  double s = 0;
+  for (int k = threadIdx.x; k < nblk; k += 256) s += part[k];
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) out[0] = s / (double)N;
+}
+
+__global__ void __launch_bounds__(256) k_ce_grad(const float* __restrict__ clog, const double* __restrict__ m01,
+                                                 const float* __restrict__ mlog, const void* __restrict__ gt,
+                                                 int gt_f64, long N, int L, int d, int HW, int mask_code,
+                                                 const double* __restrict__ gs, float* __restrict__ dcode) {
+  const double scale = (gs ? gs[0] : 1.0) / (double)N;
+  const long LHW = (long)L * HW;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < N; e += (long)gridDim.x * 256) {
+    const long b = e / LHW, r = e - b * LHW;
+    const int i = (int)(r / HW), p = (int)(r - (long)i * HW);
+    const double m = ce_mask(m01, mlog, (size_t)b * HW + p, mask_code);
+    const size_t base = ((size_t)(b * L + i) * d) * HW + p;
+    const float* x = clog + base;
+    double lse;
+    const double mx = ce_lse(x, (size_t)HW, d, m, &lse);
+    const int t = ce_target(gt, gt_f64, (size_t)e, d);
+    for (int k = 0; k < d; ++k) {
+      const double sm = exp(m * (double)x[(size_t)k * HW] - mx - lse);  // exp(log_softmax), as ATen's backward
+      dcode[base + (size_t)k * HW] = (float)(scale * (sm - (k == t ? 1.0 : 0.0)) * m);
+    }
+  }
+}
+
 static int mask_blocks(long n) {
   long b = (n + 255) / 256;
   return (int)(b > 1024 ? 1024 : (b < 1 ? 1 : b));
@@ -287,5 +365,42 @@ extern "C" int zp_mask_loss_bwd(const float* x, const float* g, long long n, con
   if (gb > 8192) gb = 8192;
   hipLaunchKernelGGL(k_mask_grad, dim3((int)gb), dim3(256), 0, (hipStream_t)stream, x, g, (long)n, grad_scale, dx);
   ZP_LAUNCH_CHECK("zp_mask_loss_bwd");
+  return ZP_OK;
+}
+
+extern "C" long long zp_ce_loss_ws_bytes(int B, int L, int H, int W) {
+  long long N = (long long)B * L * H * W;
+  return ((N + 255) / 256) * 8 + 64;
+}
+
+extern "C" int zp_ce_loss(const float* code_logits, const double* mask01, const float* mask_logits, const void* gt,
+                          int gt_f64, int B, int L, int d, int H, int W, int mask_code, double* out, void* ws,
+                          void* stream) {
+  ZP_CHECK_ARG(code_logits && gt && out && ws && (mask01 || mask_logits || !mask_code), "zp_ce_loss: null pointer");
+  ZP_CHECK_ARG(B > 0 && L >= 1 && d >= 2 && d <= 256 && H > 0 && W > 0, "zp_ce_loss: bad sizes");
+  const long long N = (long long)B * L * H * W;
+  ZP_CHECK_ARG((long long)H * W < (1ll << 31) && (N + 255) / 256 < (1ll << 31), "zp_ce_loss: too many pixels");
+  const int nblk = (int)((N + 255) / 256);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_ce_partials, dim3(nblk), dim3(256), 0, st, code_logits, mask01, mask_logits, gt, gt_f64, (long)N,
+                     L, d, H * W, mask_code, (double*)ws);
+  ZP_LAUNCH_CHECK("zp_ce_loss partials");
+  hipLaunchKernelGGL(k_ce_finalize, dim3(1), dim3(256), 0, st, (const double*)ws, nblk, (long)N, out);
+  ZP_LAUNCH_CHECK("zp_ce_loss finalize");
+  return ZP_OK;
+}
+
+extern "C" int zp_ce_loss_bwd(const float* code_logits, const double* mask01, const float* mask_logits, const void* gt,
+                              int gt_f64, int B, int L, int d, int H, int W, int mask_code, const double* grad_scale,
+                              float* dcode, void* stream) {
+  ZP_CHECK_ARG(code_logits && gt && dcode && (mask01 || mask_logits || !mask_code), "zp_ce_loss_bwd: null pointer");
+  ZP_CHECK_ARG(B > 0 && L >= 1 && d >= 2 && d <= 256 && H > 0 && W > 0 && (long long)H * W < (1ll << 31),
+               "zp_ce_loss_bwd: bad sizes");
+  const long N = (long)B * L * H * W;
+  long g = (N + 255) / 256;
+  if (g > 8192) g = 8192;
+  hipLaunchKernelGGL(k_ce_grad, dim3((int)g), dim3(256), 0, (hipStream_t)stream, code_logits, mask01, mask_logits, gt,
+                     gt_f64, N, L, d, H * W, mask_code, grad_scale, dcode);
+  ZP_LAUNCH_CHECK("zp_ce_loss_bwd");
   return ZP_OK;
 }

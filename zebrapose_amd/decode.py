@@ -1,7 +1,7 @@
 """Device code -> vertex decode, host wrapper over ``zp_decode``.
 
 ``Decoder`` keeps the class-id -> 3D LUT(s) resident on the device (f32 [n_obj][2^L][3],
-768 KB per object at L = 16) and turns a batch of network outputs into ordered 2D-3D
+768 KB per object at L = 16; d-ary codes, ``class_base=d``: [n_obj][d^L][3] through ``zp_decode_radix``) and turns a batch of network outputs into ordered 2D-3D
 correspondences without leaving the GPU:
 
     counts[b]          number of mask pixels of crop b
@@ -41,9 +41,24 @@ def read_lut_file(path):
 class Decoder:
     """Batched on-device decode for one or several objects (lut_index per crop)."""
 
-    def __init__(self, luts, device="cuda", ignore_bit=0):
+    def __init__(self, luts, device="cuda", ignore_bit=0, class_base=2):
+        """class_base d != 2: d-ary codes (the 'CE' ablation) -- the code length L is derived from
+        the LUT size d^L, ids fold as sum_i digit_i * d^(L-1-i) (``zp_decode_radix``)."""
         if isinstance(luts, np.ndarray) and luts.ndim == 2:
             luts = [luts]
+        class_base = int(class_base)
+        self.class_base = class_base
+        if class_base != 2:
+            if ignore_bit:  # generate_new_dict.py:4-33 merges children of a binary code only
+                raise ValueError("ignore_bit needs binary codes (class_base 2)")
+            n = int(np.asarray(luts[0]).shape[0])
+            steps, m = 0, 1
+            while m < n:
+                m, steps = m * class_base, steps + 1
+            if class_base < 2 or class_base > 256 or class_base & (class_base - 1) or m != n or n > 2 ** 24:
+                raise ValueError(f"a LUT of {n} classes is no power (<= 2^24) of class_base {class_base}, or "
+                                 "class_base is no power of two in [2, 256]")
+            self.steps = steps
         full_bits = int(round(np.log2(np.asarray(luts[0]).shape[0])))
         self.full_bits = full_bits
         self.ignore_bit = ignore_bit
@@ -66,7 +81,10 @@ class Decoder:
         code_logits = code_logits.detach().contiguous().float()
         B, _, H, W = mask_logits.shape
         Lfull = code_logits.shape[1]
-        if Lfull < self.bits:
+        if self.class_base != 2:
+            if Lfull != self.steps * self.class_base:
+                raise ValueError(f"expected {self.steps} x {self.class_base} code channels, got {Lfull}")
+        elif Lfull < self.bits:
             raise ValueError("fewer code channels than LUT bits")
         dev = mask_logits.device
         if torch.is_tensor(bboxes) and bboxes.device == dev and bboxes.dtype == torch.int32:
@@ -81,9 +99,14 @@ class Decoder:
         xyz = torch.empty((B, H * W, 3), dtype=torch.float32, device=dev)
         ids = torch.empty((B, H, W), dtype=torch.int32, device=dev) if return_ids else None
         ws = torch.empty(int(L.lib.zp_decode_ws_bytes(B, H, W)), dtype=torch.uint8, device=dev)
-        L.call("zp_decode", mask_logits.data_ptr(), code_logits.data_ptr(), B, H, W, Lfull, self.bits,
-               self.lut.data_ptr(), L.ptr(li), bb.data_ptr(), int(bbox_size), L.ptr(ids), counts.data_ptr(),
-               xy.data_ptr(), xyz.data_ptr(), ws.data_ptr(), L.stream_ptr())
+        if self.class_base != 2:
+            L.call("zp_decode_radix", mask_logits.data_ptr(), code_logits.data_ptr(), B, H, W, self.steps,
+                   self.class_base, self.lut.data_ptr(), L.ptr(li), bb.data_ptr(), int(bbox_size), L.ptr(ids),
+                   counts.data_ptr(), xy.data_ptr(), xyz.data_ptr(), ws.data_ptr(), L.stream_ptr())
+        else:
+            L.call("zp_decode", mask_logits.data_ptr(), code_logits.data_ptr(), B, H, W, Lfull, self.bits,
+                   self.lut.data_ptr(), L.ptr(li), bb.data_ptr(), int(bbox_size), L.ptr(ids), counts.data_ptr(),
+                   xy.data_ptr(), xyz.data_ptr(), ws.data_ptr(), L.stream_ptr())
         if return_ids:
             return counts, xy, xyz, ids
         return counts, xy, xyz

@@ -112,6 +112,51 @@ class Unit:
         return G.out_size(IH, self.k, self.s, self.p, self.d), G.out_size(IW, self.k, self.s, self.p, self.d)
 
 
+class PackedHead:
+    """ASPP_non_binary_ablationstudy's two head convs (aspp.py:281-282, 337-338: the same input, 1 and
+    L * d output channels) seen as ONE conv of 1 + L * d channels: row 0 of ``weight`` / ``bias`` is
+    conv_1x1_4_mask, rows 1.. are conv_1x1_4_code, so ZP_OUT_HEAD_NCHW's channel-0 / rest split sends
+    each to its own output.  The packed tensors keep their storage and are refreshed in place when a
+    part's version changes (their own version then moves, which is what the weight packings are
+    cached on); ``split`` hands a packed gradient back to the four parameters."""
+
+    def __init__(self, mask_conv, code_conv):
+        self.parts = (mask_conv, code_conv)
+        self.kernel_size, self.stride = mask_conv.kernel_size, mask_conv.stride
+        self.padding, self.dilation = mask_conv.padding, mask_conv.dilation
+        self.in_channels = mask_conv.in_channels
+        self.out_channels = mask_conv.out_channels + code_conv.out_channels
+        self.weight = self.bias = None
+        self._ver = None
+
+    def refresh(self):
+        m, c = self.parts
+        ver = tuple((t._version, t.data_ptr()) for t in (m.weight, m.bias, c.weight, c.bias))
+        if ver == self._ver:
+            return
+        with torch.no_grad():
+            if self.weight is None or self.weight.device != m.weight.device:
+                self.weight = torch.cat([m.weight.detach(), c.weight.detach()]).contiguous()
+                self.bias = torch.cat([m.bias.detach(), c.bias.detach()]).contiguous()
+            else:
+                n = m.out_channels
+                self.weight[:n].copy_(m.weight)
+                self.weight[n:].copy_(c.weight)
+                self.bias[:n].copy_(m.bias)
+                self.bias[n:].copy_(c.bias)
+        self._ver = ver
+
+    def split(self, key, grad):
+        """(parameter, gradient) pairs of one packed gradient (views of it, row 0 / rows 1..)."""
+        m, c = self.parts
+        n = m.out_channels
+        if key is self.weight:
+            return ((m.weight, grad[:n]), (c.weight, grad[n:]))
+        if key is self.bias:
+            return ((m.bias, grad[:n]), (c.bias, grad[n:]))
+        return ((key, grad),)
+
+
 class Tape:
     def __init__(self):
         self.recs = []
@@ -180,6 +225,7 @@ class Engine:
         self._rflag = None
         self.unread_packs = False
         self.range_probe = None  # optional list (tests): see _probe
+        self._head_pack = None  # the d-ary network's two head convs as one (head_conv)
 
     def range_word(self, device):
         """This engine's zp_split_range_flag word on ``device`` (int32 [1]): raised by any of its
@@ -562,6 +608,17 @@ class Engine:
         elif self.trace is not None:
             self.trace.append(("head", unit, x, (mask, code), None))
 
+    def head_conv(self):
+        """The network's head as one conv: aspp.conv_1x1_4, or the d-ary network's conv_1x1_4_mask /
+        conv_1x1_4_code pair packed into one (PackedHead, refreshed from the parameters here)."""
+        aspp = self._net().aspp
+        if hasattr(aspp, "conv_1x1_4"):
+            return aspp.conv_1x1_4
+        if self._head_pack is None or self._head_pack.parts != (aspp.conv_1x1_4_mask, aspp.conv_1x1_4_code):
+            self._head_pack = PackedHead(aspp.conv_1x1_4_mask, aspp.conv_1x1_4_code)
+        self._head_pack.refresh()
+        return self._head_pack
+
     def _stem_direct_ok(self, unit, OH, OW, out_ld, out_c0, x_ld):
         """The one-launch two-plane stem (zp_stem_split) takes this 7x7 / s2 conv: split stem on,
         output width <= 128 dividing 256, whole 256-pixel tiles, 16-byte output rows and input rows
@@ -587,6 +644,8 @@ class Engine:
         eval forward, no trace, and -- two-plane engine -- the 256 x 256 tile eligible at this grid, or
         -- bf16 / fp16 -- the strip tile (conv + per-cout-tile head partials, then their combine)."""
         if self.dt not in (L.ZP_F32H2, L.ZP_BF16, L.ZP_F16) or not self.fuse_head or self.trace is not None:
+            return False
+        if self.head_conv().out_channels > 32:  # zp_conv2d_head: hcout <= 32 (the d-ary code heads are wider)
             return False
         a = L.ConvArgs()
         a.dtype, a.Cin, a.Cout, a.N, a.GH, a.GW, a.IH, a.IW = self.dt, 256, 256, B, H, W, H, W
@@ -767,6 +826,12 @@ class Engine:
         def dest(p):
             v = sink_dest(p) if sink_dest is not None else None
             return torch.empty_like(p) if v is None else v
+
+        split = getattr(conv, "split", None)  # PackedHead: one gradient -> its parameters' gradients
+
+        def hand(k, v):
+            for p_, g_ in (((k, v),) if split is None else split(k, v)):
+                grads[p_] = g_
         tr = None if self.bwd_trace is None else {"kind": kind, "unit": unit, "x": x, "out": out, "res": res,
                                                    "raw": raw, "save": save}
         if kind == "head":
@@ -825,8 +890,8 @@ class Engine:
             dw = dest(conv.weight)
             self._wgrad(unit, x, plan, wdy, dw)
             for k, v in pending.items():  # (item by item: dict.update would bypass _ReadyDict's reporting)
-                grads[k] = v
-            grads[conv.weight] = dw
+                hand(k, v)
+            hand(conv.weight, dw)
         else:
             # the side stream starts after everything enqueued so far (gy, dgamma / dbeta, the head
             # bias); the gradients are handed over (grads / GradBuckets.ready copies) from the side
@@ -840,8 +905,8 @@ class Engine:
             with torch.cuda.stream(side):
                 self._wgrad(unit, x, plan, wdy, dw)
                 for k, v in pending.items():
-                    grads[k] = v
-                grads[conv.weight] = dw
+                    hand(k, v)
+                hand(conv.weight, dw)
             gy.buf.record_stream(side)  # freed below on the main stream; reused only after the wgrad
             self._side_used = True  # x (the tape's activation) and the gradients outlive the join
         if tr is not None:
@@ -947,6 +1012,7 @@ class Engine:
             # (a chunked forward clears it before its first chunk only: the word covers the batch)
             if first and (not self.unread_packs or torch.cuda.is_current_stream_capturing()):
                 flag.zero_()
+        head_conv = self.head_conv()  # (before the batched repack: a refreshed packed head is repacked with the rest)
         self._prepack(dev)
         st = L.stream_ptr()
         self.stage = "stem"
@@ -1015,16 +1081,16 @@ class Engine:
         self.stage = "up1"
         self._upsample(aspp.upsample_1, o, Act(up2_in, 0, 256), tape)
         self.stage = "up2"
-        ncls = aspp.conv_1x1_4.out_channels
+        ncls = head_conv.out_channels
         mask = torch.empty((B, 1, H2, W2), dtype=torch.float32, device=dev)
         code = torch.empty((B, ncls - 1, H2, W2), dtype=torch.float32, device=dev)
         if fuse:
             self._upsample(aspp.upsample_2, Act(up2_in), None, tape,
-                           head=(self._u(aspp.conv_1x1_4, None, False), x128, mask, code))
+                           head=(self._u(head_conv, None, False), x128, mask, code))
         else:
             self._upsample(aspp.upsample_2, Act(up2_in), Act(head_in, 0, 256), tape)
             self.stage = "head"
-            self.head_fwd(self._u(aspp.conv_1x1_4, None, False), Act(head_in), mask, code, tape)
+            self.head_fwd(self._u(head_conv, None, False), Act(head_in), mask, code, tape)
         r = {"mask": mask, "code": code, "tape": tape, "xh": xh, "x64": x64, "x128": x128}
         if tape is not None and self.bwd_trace is not None:
             self.last_fwd = r  # the traced training step's outputs and tape (teacher-forced tests)

@@ -157,6 +157,9 @@ class GraphedTrainStep:
             raise ValueError("GraphedTrainStep runs single-process steps (no data-parallel wrapper)")
         if not getattr(ts.optimizer, "capturable", False):
             raise ValueError("GraphedTrainStep needs TrainStep(..., capturable=True)")
+        if ts.code_loss.binary_code_loss_type != "BCE":
+            raise NotImplementedError("GraphedTrainStep captures the binary-code ('BCE') step only; run the d-ary "
+                                      "'CE' step through TrainStep")
         self.ts = ts
         self.x, self.gc, self.gm = x.clone(), gt_code.clone(), gt_mask.clone()
         dev = self.x.device

@@ -34,7 +34,7 @@ from .. import _lib as L
 from .. import staged as _staged
 from ..engine import Engine
 from ..parallel import finish_grads, grads_sink
-from .aspp import ASPP, ASPP_50
+from .aspp import ASPP, ASPP_50, ASPP_non_binary_ablationstudy
 from .resnet import ResNet34_OS8, ResNet50_OS8
 
 SPLIT_FORMS = ("x3", "h2")  # include/zp.h ZP_F32X3 / ZP_F32H2
@@ -84,16 +84,63 @@ class _CodeLossFn(torch.autograd.Function):
         return dcode, None, None, None, None, None, None
 
 
+class _CELossFn(torch.autograd.Function):
+    """zp_ce_loss / zp_ce_loss_bwd: the 'CE' branch (BinaryCodeNet.py:47-48, 57-60, 65) over
+    code logits [B, L * d, H, W] and digit planes [B, L, H, W]."""
+
+    @staticmethod
+    def forward(ctx, code, mask01, mask_logits, gt, d, mask_code):
+        code = code.contiguous()
+        B, Ld, H, W = code.shape
+        if Ld % d:
+            raise ValueError(f"{Ld} code channels are no multiple of {d} classes per step")
+        Lc = Ld // d
+        if tuple(gt.shape) != (B, Lc, H, W):
+            raise ValueError(f"expected digit planes {(B, Lc, H, W)}, got {tuple(gt.shape)}")
+        gt_f64 = 1 if gt.dtype == torch.float64 else 0
+        if not gt_f64:
+            gt = gt.to(torch.uint8)
+        gt = gt.contiguous()
+        dev = code.device
+        ws = torch.empty(int(L.lib.zp_ce_loss_ws_bytes(B, Lc, H, W)), dtype=torch.uint8, device=dev)
+        out = torch.empty(1, dtype=torch.float64, device=dev)
+        L.call("zp_ce_loss", code.data_ptr(), L.ptr(mask01), L.ptr(mask_logits), gt.data_ptr(), gt_f64, B, Lc, d, H, W,
+               int(mask_code), out.data_ptr(), ws.data_ptr(), L.stream_ptr())
+        ctx.save_for_backward(code, mask01 if mask01 is not None else mask_logits, gt)
+        ctx.meta = (mask01 is not None, gt_f64, mask_code, d)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        code, m, gt = ctx.saved_tensors
+        is01, gt_f64, mask_code, d = ctx.meta
+        B, Ld, H, W = code.shape
+        g = g.to(torch.float64).contiguous()
+        dcode = torch.empty_like(code)
+        L.call("zp_ce_loss_bwd", code.data_ptr(), m.data_ptr() if is01 else None, None if is01 else m.data_ptr(),
+               gt.data_ptr(), gt_f64, B, Ld // d, d, H, W, int(mask_code), g.data_ptr(), dcode.data_ptr(),
+               L.stream_ptr())
+        return dcode, None, None, None, None, None
+
+
 class BinaryCodeLoss(nn.Module):
-    """BinaryCodeNet.py:8-67.  Device implementation of the configuration the trainers use
-    ('BCE', mask_binary_code_loss, histogram-weighted or plain); 'L1' / 'CE' are ablation
-    branches outside the hot path."""
+    """BinaryCodeNet.py:8-67.  Device implementations: 'BCE' (mask_binary_code_loss,
+    histogram-weighted or plain -- the trainers' configuration) and 'CE' (the d-ary code
+    ablation, config_ablation/exp_lmo_ablation_*: softmax cross-entropy over each step's
+    ``divided_number_each_iteration`` class logits); 'L1' is a binary ablation branch outside
+    the hot path."""
 
     def __init__(self, binary_code_loss_type, mask_binary_code_loss, divided_number_each_iteration,
                  use_histgramm_weighted_binary_loss=False):
         super().__init__()
-        if binary_code_loss_type != "BCE":
-            raise NotImplementedError(f"binary code loss type {binary_code_loss_type!r}: only 'BCE' runs on device")
+        if binary_code_loss_type not in ("BCE", "CE"):
+            raise NotImplementedError(f"binary code loss type {binary_code_loss_type!r}: only 'BCE' and 'CE' run "
+                                      "on device")
+        if use_histgramm_weighted_binary_loss and binary_code_loss_type != "BCE":
+            # BinaryCodeNet.py:28-29 asserts the same
+            raise AssertionError("use_histgramm_weighted_binary_loss is implemented for 'BCE' only")
+        if binary_code_loss_type == "CE" and not 2 <= int(divided_number_each_iteration) <= 256:
+            raise ValueError("'CE' needs 2 <= divided_number_each_iteration <= 256")
         self.binary_code_loss_type = binary_code_loss_type
         self.mask_binary_code_loss = mask_binary_code_loss
         self.divided_number_each_iteration = divided_number_each_iteration
@@ -116,12 +163,18 @@ class BinaryCodeLoss(nn.Module):
         """pred_mask: the 0/1 mask (f64 in the reference, train_v6.py:325-326)."""
         if pred_mask.dtype != torch.float64:
             pred_mask = pred_mask.to(torch.float64)
+        if self.binary_code_loss_type == "CE":
+            return _CELossFn.apply(pred_binary_code, pred_mask.contiguous(), None, groundtruth_code,
+                                   int(self.divided_number_each_iteration), self.mask_binary_code_loss)
         st = self._state(pred_binary_code.shape[1], pred_binary_code.device)
         return _CodeLossFn.apply(pred_binary_code, pred_mask.contiguous(), None, groundtruth_code, st,
                                  self.use_histgramm_weighted_binary_loss, self.mask_binary_code_loss)
 
     def forward_from_logits(self, pred_binary_code, pred_mask_logits, groundtruth_code):
         """Same loss with the mask thresholded on device from the mask logits (no host round trip)."""
+        if self.binary_code_loss_type == "CE":
+            return _CELossFn.apply(pred_binary_code, None, pred_mask_logits.detach().contiguous(), groundtruth_code,
+                                   int(self.divided_number_each_iteration), self.mask_binary_code_loss)
         st = self._state(pred_binary_code.shape[1], pred_binary_code.device)
         return _CodeLossFn.apply(pred_binary_code, None, pred_mask_logits.detach().contiguous(), groundtruth_code, st,
                                  self.use_histgramm_weighted_binary_loss, self.mask_binary_code_loss)
@@ -219,6 +272,9 @@ class DeepLabV3(nn.Module):
             self.aspp = ASPP_50(num_classes=self.num_classes, concat=concat, output_kernel_size=output_kernel_size)
         else:
             raise NotImplementedError("num_resnet_layers must be 34 or 50")
+        self._init_engine(precision)
+
+    def _init_engine(self, precision):
         prec = precision or os.environ.get("ZP_PRECISION", "fp32")
         object.__setattr__(self, "_engine", Engine(self, _PREC[prec]))
         object.__setattr__(self, "_engines_split", {})
@@ -293,6 +349,34 @@ class DeepLabV3(nn.Module):
         return mask, code
 
 
+class DeepLabV3_non_binary(DeepLabV3):
+    """BinaryCodeNet.py:177-196: the d-ary code network of the code-radix ablation (ResNet34 encoder
+    only, as in the reference) -- DeepLabV3 with ASPP_non_binary_ablationstudy's head pair;
+    ``forward(x) -> (mask_logits [B, 1, H/2, W/2], code_logits [B, L * d, H/2, W/2])``.  The engine
+    runs the two head convs as one head launch of 1 + L * d channels (engine.PackedHead); precision,
+    the split-fp32 eval engines with their range guard and the training path are DeepLabV3's."""
+
+    # class ids are decoded as integers of at most 24 bits (zp_decode_radix, the LUT's 2^24 rows)
+    MAX_ID_BITS = 24
+
+    def __init__(self, num_resnet_layers, binary_code_length=16, divided_number_each_iteration=2, concat=False,
+                 output_kernel_size=1, precision=None):
+        nn.Module.__init__(self)
+        d, Lc = int(divided_number_each_iteration), int(binary_code_length)
+        if d < 2 or d > 256 or d & (d - 1) or Lc < 1 or Lc * (d.bit_length() - 1) > self.MAX_ID_BITS:
+            raise NotImplementedError(f"{Lc} steps of {d} classes: the d-ary code path takes d a power of two in "
+                                      f"[2, 256] and class ids of at most {self.MAX_ID_BITS} bits")
+        self.concat = concat
+        self.num_resnet_layers = 34  # BinaryCodeNet.py:182 ignores num_resnet_layers
+        self.binary_code_length = Lc
+        self.divided_number_each_iteration = d
+        self.num_classes = 1 + Lc * d
+        self.resnet = ResNet34_OS8(34, concat)
+        self.aspp = ASPP_non_binary_ablationstudy(code_output_length=Lc, divided_number_each_iteration=d,
+                                                  concat=concat, output_kernel_size=output_kernel_size)
+        self._init_engine(precision)
+
+
 class BinaryCodeNet_Deeplab(nn.Module):
     """BinaryCodeNet.py:122-143."""
 
@@ -300,11 +384,14 @@ class BinaryCodeNet_Deeplab(nn.Module):
                  output_kernel_size=1, precision=None):
         super().__init__()
         self.concat = concat
-        if divided_number_each_iteration != 2:
-            raise NotImplementedError("DeepLabV3_non_binary (CE ablation, BinaryCodeNet.py:177-196) is outside "
-                                      "the hot path")
-        self.net = DeepLabV3(num_resnet_layers, binary_code_length + 1, concat=self.concat,
-                             output_kernel_size=output_kernel_size, precision=precision)
+        if divided_number_each_iteration == 2:
+            self.net = DeepLabV3(num_resnet_layers, binary_code_length + 1, concat=self.concat,
+                                 output_kernel_size=output_kernel_size, precision=precision)
+        else:  # BinaryCodeNet.py:139-140
+            self.net = DeepLabV3_non_binary(num_resnet_layers, binary_code_length=binary_code_length,
+                                            divided_number_each_iteration=divided_number_each_iteration,
+                                            concat=self.concat, output_kernel_size=output_kernel_size,
+                                            precision=precision)
 
     def set_precision(self, precision):
         self.net.set_precision(precision)

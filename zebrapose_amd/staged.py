@@ -37,7 +37,7 @@ def stage_of(name):
         return "up1"
     if name.startswith("aspp.upsample_2."):
         return "up2"
-    if name.startswith("aspp.conv_1x1_4."):
+    if name.startswith("aspp.conv_1x1_4"):  # (conv_1x1_4, or the d-ary network's conv_1x1_4_mask / _code)
         return "head"
     if name.startswith("aspp."):
         return "aspp"

@@ -30,7 +30,11 @@ def scale_for_world(learning_rate, total_iteration, world_size):
 
 class TrainStep:
     def __init__(self, net, learning_rate=2e-4, binary_loss_weight=3.0, ddp=None, device=None, bucket_mb=25.0,
-                 capturable=False):
+                 capturable=False, binary_code_loss_type="BCE", divided_number_each_iteration=2,
+                 use_histgramm_weighted_binary_loss=True):
+        """binary_code_loss_type "CE" with divided_number_each_iteration d: the d-ary code ablation
+        (config_ablation/exp_lmo_ablation_*: BinaryCodeLoss('CE', True, d, False), gt_code = digit
+        planes); the defaults are train_v6.py's step."""
         self.module = net
         self.net = net
         if ddp is None:
@@ -44,7 +48,11 @@ class TrainStep:
                 dev = device if device is not None else torch.cuda.current_device()
                 self.net = torch.nn.parallel.DistributedDataParallel(net, device_ids=[dev])
         self.binary_loss_weight = binary_loss_weight
-        self.code_loss = BinaryCodeLoss("BCE", True, 2, use_histgramm_weighted_binary_loss=True)
+        if binary_code_loss_type == "CE":
+            self.code_loss = BinaryCodeLoss("CE", True, divided_number_each_iteration, False)
+        else:
+            self.code_loss = BinaryCodeLoss(binary_code_loss_type, True, divided_number_each_iteration,
+                                            use_histgramm_weighted_binary_loss=use_histgramm_weighted_binary_loss)
         self.mask_loss = MaskLoss()
         # capturable: device-side Adam step counts, for zebrapose_amd.graphs.GraphedTrainStep
         self.optimizer = FusedAdam(self.net.parameters(), lr=learning_rate, capturable=capturable)
