@@ -32,6 +32,8 @@
  *   zp_ce_loss, zp_code_digits, zp_decode_radix, zp_pack_digits
  *                      the d-ary code ablation (config_ablation/exp_lmo_ablation_*: 'CE' loss,
  *                      common_ops.py:21-28, class_id_encoder_decoder.py:17-28, 43-63)
+ *   zp_augment         apply_augmentation (bop_dataset_pytorch.py:349-355): the imgaug colour chain of
+ *                      GDR_Net_Augmentation.py:161-178 ahead of the is_train crop (:267-277)
  *   zp_adam            torch.optim.Adam step used by train_v6.py:268-269, 338
  */
 #ifndef ZP_H_
@@ -494,6 +496,41 @@ int zp_crop_gt(const uint8_t* gts, const uint8_t* masks, const uint8_t* entire_m
  * the reference's class_id_image_to_class_code_images(id, d, 16/s, 65536)
  * (class_id_encoder_decoder.py:43-63): digit_i = (id >> s*(L-1-i)) & (d-1).  nbits % s == 0, s <= 8 */
 int zp_pack_digits(const uint8_t* bits, int B, int nbits, int H, int W, int s, uint8_t* digits, void* stream);
+
+/* ---- training-branch colour augmentation on the device -------------------------------------
+ * Replaces apply_augmentation (bop_dataset_pytorch.py:349-355): the imgaug chain of
+ * GDR_Net_Augmentation.build_augmentations (GDR_Net_Augmentation.py:161-178), Sequential in fixed
+ * order, run over the image before the is_train crop (bop_dataset_pytorch.py:267-277).  The host
+ * samples every random choice (zebrapose_amd/augment.py); the device does exact integer pixel work,
+ * u8 -> u8 per stage, one flag bit per stage:
+ *   ZP_AUG_SP       SaltAndPepper: h1 = fmix(sp_seed ^ ((y W + x) 0x9E3779B9)) (uint32, fmix = murmur3's
+ *                   finaliser); when h1 < sp_thresh all three channels become
+ *                   beta_tab[fmix(h1 ^ 0x68bc21eb) >> 24]
+ *   ZP_AUG_STENCIL_A  MotionBlur: out = min(255, (sum kA[i][j] in[y+i-2][x+j-2] + 32768) >> 16), kA >= 0 with
+ *                   sum 65536, BORDER_REFLECT_101 on the full image
+ *   ZP_AUG_DROPOUT  CoarseDropout: keep-mask masks[b][mh][mw] nearest-upsampled (my = min(floor(y (1 /
+ *                   (H / mh))), mh - 1)); a dropped pixel becomes 0 in all channels
+ *   ZP_AUG_STENCIL_B  GaussianBlur: the same stencil with kB, its reflected border reading the dropout
+ *                   stage's output at the in-image position
+ *   ZP_AUG_LUT      Add / Invert / Multiply x 2 / LinearContrast composed: c = luts[b][c][v]
+ * imgs u8 [n_img][H][W][3]; crop b reads image img_index[b]; out u8 [B][H][W][3].  flags == 0 copies.
+ * bbox NULL: every pixel of out is written.  bbox int32 [B][4] (the box handed to zp_crop_image):
+ * only the 32 x 32 tiles meeting the region crop_square_resize copies, [max(x1, 0), xe) x [max(y1, 0), ye),
+ * are written (a zero box writes nothing); the rest of out keeps its contents.
+ * H, W >= 8; 1 <= mh <= H, 1 <= mw <= W; all of masks, luts, beta_tab are required. */
+#define ZP_AUG_SP 1
+#define ZP_AUG_STENCIL_A 2
+#define ZP_AUG_DROPOUT 4
+#define ZP_AUG_STENCIL_B 8
+#define ZP_AUG_LUT 16
+typedef struct {
+  uint32_t flags;
+  uint32_t sp_seed, sp_thresh;
+  int32_t kA[25], kB[25]; /* [5][5], Q16 */
+} zp_aug_desc;
+int zp_augment(const uint8_t* imgs, int n_img, int H, int W, const int* img_index, const zp_aug_desc* desc,
+               const uint8_t* masks, int mh, int mw, const uint8_t* luts, const uint8_t* beta_tab, const int* bbox,
+               int B, uint8_t* out, void* stream);
 
 /* ---- optimizer ----------------------------------------------------------------------- */
 /* torch.optim.Adam (no weight decay, amsgrad off) over one flat f32 buffer; step >= 1 */

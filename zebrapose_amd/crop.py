@@ -10,6 +10,11 @@ image and masks), turns the GT colours into 16 code planes (``RGB_image_to_class
 per crop, same functions as the reference) and the pixel work is two kernels over a whole batch
 (``zp_crop_image``, ``zp_crop_gt``, csrc/zp_crop.hip) reading images resident in HBM.
 Only ``resize_method="crop_square_resize"`` (the configs' method) is on the device.
+
+``CropPipeline.train_batch`` is the ``is_train`` branch (:267-277): ``aug_Bbox`` jitters the box
+on the host, ``zp_augment`` (augment.py) runs the imgaug colour chain over the part of the image
+the crop reads, and the same two crop kernels follow.  numpy's global RNG of the reference is a
+``np.random.Generator`` here, so the draws differ from the reference's for a given seed.
 """
 from __future__ import annotations
 
@@ -27,6 +32,20 @@ def padding_Bbox(Bbox, padding_ratio):
     bh, bw = y2 - y1, x2 - x1
     pbw, pbh = int(bw * padding_ratio), int(bh * padding_ratio)
     return np.array([int(cx - pbw / 2), int(cy - pbh / 2), int(pbw), int(pbh)])
+
+
+def aug_Bbox(GT_Bbox, padding_ratio, rng):
+    """bop_dataset_pytorch.py:141-160 with ``rng.random()`` then ``rng.random(2)`` for the two
+    np.random.random_sample calls."""
+    x1, x2 = GT_Bbox[0], GT_Bbox[0] + GT_Bbox[2]
+    y1, y2 = GT_Bbox[1], GT_Bbox[1] + GT_Bbox[3]
+    cx, cy = 0.5 * (x1 + x2), 0.5 * (y1 + y2)
+    bh, bw = y2 - y1, x2 - x1
+    scale_ratio = 1 + 0.25 * (2 * rng.random() - 1)  # [1 - 0.25, 1 + 0.25]
+    shift_ratio = 0.25 * (2 * rng.random(2) - 1)  # [-0.25, 0.25]
+    center = np.array([cx + bw * shift_ratio[0], cy + bh * shift_ratio[1]])
+    abw, abh = int(bw * scale_ratio * padding_ratio), int(bh * scale_ratio * padding_ratio)
+    return np.array([int(center[0] - abw / 2), int(center[1] - abh / 2), abw, abh])
 
 
 def get_final_Bbox(Bbox, resize_method, max_x, max_y):
@@ -101,6 +120,12 @@ class CropPipeline:
         """images u8 [N, H, W, 3] (BGR, device); img_index int [B]; boxes = padded boxes int [B, 4].
         Returns dict: x f32 [B, 3, S_img, S_img] and, when the GT inputs are given, code u8
         [B, L, S_gt, S_gt] (bit planes, or the d-ary digits for class_base d), mask / entire_mask f32 [B, S_gt, S_gt]."""
+        images, gt_images, masks, entire_masks, ii = self._check(images, img_index, gt_images, masks, entire_masks)
+        bb = torch.as_tensor(np.asarray(boxes), dtype=torch.int32).reshape(len(ii), 4).to(images.device).contiguous()
+        return self._crop(images, ii, bb, gt_images, masks, entire_masks, ii)
+
+    @staticmethod
+    def _check(images, img_index, gt_images, masks, entire_masks):
         images = _u8(images, "images", 4)
         gt_images = _u8(gt_images, "gt_images", 4)
         masks = _u8(masks, "masks", 3)
@@ -111,27 +136,62 @@ class CropPipeline:
         for t in (gt_images, masks, entire_masks):
             if t is not None and (t.shape[0] != N or t.shape[1] != H or t.shape[2] != W):
                 raise ValueError("GT images / masks must match the image stack")
-        dev = images.device
         idx = np.asarray(img_index, dtype=np.int64).reshape(-1)
-        B = len(idx)
-        if B == 0 or idx.min() < 0 or idx.max() >= N:
+        if len(idx) == 0 or idx.min() < 0 or idx.max() >= N:
             raise ValueError("img_index out of range")
-        ii = torch.from_numpy(idx.astype(np.int32)).to(dev)
-        bb = torch.as_tensor(np.asarray(boxes), dtype=torch.int32).reshape(B, 4).to(dev).contiguous()
+        return images, gt_images, masks, entire_masks, torch.from_numpy(idx.astype(np.int32)).to(images.device)
+
+    def _crop(self, images, ii, bb, gt_images, masks, entire_masks, gt_ii):
+        """The two crop kernels: crop b reads images[ii[b]] and the GT stacks' image gt_ii[b]."""
+        N, H, W, _ = images.shape
+        B = len(ii)
+        dev = images.device
         st = L.stream_ptr()
         out = {"x": torch.empty((B, 3, self.S_img, self.S_img), dtype=torch.float32, device=dev)}
         L.call("zp_crop_image", images.data_ptr(), N, H, W, ii.data_ptr(), bb.data_ptr(), B, self.S_img,
                out["x"].data_ptr(), st)
         if gt_images is not None or masks is not None or entire_masks is not None:
             S = self.S_gt
+            Ng = next(t for t in (gt_images, masks, entire_masks) if t is not None).shape[0]
             code = torch.empty((B, self.L, S, S), dtype=torch.uint8, device=dev) if gt_images is not None else None
             m = torch.empty((B, S, S), dtype=torch.float32, device=dev) if masks is not None else None
             e = torch.empty((B, S, S), dtype=torch.float32, device=dev) if entire_masks is not None else None
-            L.call("zp_crop_gt", L.ptr(gt_images), L.ptr(masks), L.ptr(entire_masks), N, H, W, ii.data_ptr(),
+            L.call("zp_crop_gt", L.ptr(gt_images), L.ptr(masks), L.ptr(entire_masks), Ng, H, W, gt_ii.data_ptr(),
                    bb.data_ptr(), B, S, self.L, L.ptr(code), L.ptr(m), L.ptr(e), st)
             if code is not None and self.digit_bits:  # the 16 bit planes -> 16 / s digit planes (zp_pack_digits)
                 digits = torch.empty((B, 16 // self.digit_bits, S, S), dtype=torch.uint8, device=dev)
                 L.call("zp_pack_digits", code.data_ptr(), B, 16, S, S, self.digit_bits, digits.data_ptr(), st)
                 code = digits
             out.update(code=code, mask=m, entire_mask=e)
+        return out
+
+    def train_boxes(self, Bboxes, img_w, img_h, rng):
+        """``boxes`` for the training branch: aug_Bbox in place of padding_Bbox (:270, :277)."""
+        aug, fin = [], []
+        for bb in np.asarray(Bboxes).reshape(-1, 4):
+            a = aug_Bbox(bb, self.padding_ratio, rng)
+            aug.append(a)
+            fin.append(get_final_Bbox(a, "crop_square_resize", img_w, img_h))
+        return np.stack(aug).astype(np.int32), np.stack(fin).astype(np.int64)
+
+    def train_batch(self, images, img_index, raw_boxes, gt_images, masks, entire_masks, sampler):
+        """The ``is_train`` branch (bop_dataset_pytorch.py:267-277) for a batch: raw_boxes [B, 4] are
+        the GT ``bbox_visib`` boxes; ``sampler`` (augment.AugmentSampler) supplies the colour chain's
+        draws and, through ``sampler.rng``, aug_Bbox's.  aug boxes -> zp_augment over each crop's
+        copied region -> zp_crop_image on the augmented stack -> zp_crop_gt on the untouched GT
+        stacks.  Returns ``__call__``'s dict plus ``final_boxes`` (int64 [B, 4], get_final_Bbox) and
+        ``boxes`` (the augmented boxes, int32 [B, 4])."""
+        from .augment import augment_images
+        images, gt_images, masks, entire_masks, ii = self._check(images, img_index, gt_images, masks, entire_masks)
+        N, H, W, _ = images.shape
+        B = len(ii)
+        aug_boxes, final_boxes = self.train_boxes(raw_boxes, W, H, sampler.rng)
+        if len(aug_boxes) != B:
+            raise ValueError("raw_boxes and img_index disagree on the batch size")
+        batch = sampler.sample(B, H, W)
+        bb = torch.from_numpy(aug_boxes).to(images.device)
+        aug = augment_images(images, ii, batch, bbox=bb)
+        out = self._crop(aug, torch.arange(B, dtype=torch.int32, device=images.device), bb, gt_images, masks,
+                         entire_masks, ii)
+        out.update(final_boxes=final_boxes, boxes=aug_boxes, aug=batch)
         return out

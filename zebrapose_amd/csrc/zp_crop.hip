@@ -16,6 +16,8 @@
 //   INTER_NEAREST: sx = min(floor(dx * (1 / (dsize / ssize))), ssize - 1).
 // One thread per output pixel; the source image stays in HBM/L2 (one crop reads at most its
 // ROI once), outputs are written coalesced.
+// The training branch's colour augmentation (apply_augmentation, :349-355) runs ahead of the image
+// crop as one fused tile kernel (k_augment below, zp_augment), sharing crop_geo with the crops.
 #include <math.h>
 #include "zp_common.h"
 
@@ -187,6 +189,153 @@ __global__ void __launch_bounds__(256) k_pack_digits(const uint8_t* __restrict__
   digits[((size_t)b * L + i) * HW + p] = (uint8_t)v;
 }
 
+// ---- training-branch colour augmentation (zp_augment, include/zp.h) ---------------------------
+// One workgroup per AUG_T x AUG_T output tile and crop, fused through two LDS planes of packed
+// B | G << 8 | R << 16 pixels:
+//   p0: stage 0 (salt and pepper) of the tile + 4 px halo, loaded from the reflected in-image position
+//   p1: stages 1-2 (stencil A, coarse dropout) of the tile + 2 px halo
+//   out: stages 3-4 (stencil B, LUT) -> byte tile in LDS -> coalesced stores
+// Every plane entry is indexed by its UNREFLECTED coordinate c and holds the stage's value AT
+// reflect101(c): a p1 entry outside the image is stencil A evaluated around the in-image pixel it
+// mirrors (whose own taps are in p0, see the index bounds below), not stencil A over a mirrored
+// extension of stage 0 -- the two differ for an asymmetric (motion) kernel.
+constexpr int AUG_T = 32, AUG_P0 = AUG_T + 8, AUG_P1 = AUG_T + 4;
+
+struct AugDesc {  // = zp_aug_desc
+  uint32_t flags, sp_seed, sp_thresh;
+  int kA[25], kB[25];
+};
+
+__device__ __forceinline__ int reflect101(int c, int n) {  // one reflection (|overhang| <= n - 1), then clamped
+  c = c < 0 ? -c : c;
+  c = c >= n ? 2 * n - 2 - c : c;
+  return max(0, min(n - 1, c));
+}
+
+__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  h ^= h >> 16;
+  return h;
+}
+
+// 5 x 5 Q16 stencil around p[0] (row stride ld) on packed pixels
+__device__ __forceinline__ uint32_t stencil5(const uint32_t* p, int ld, const int* __restrict__ k) {
+  int a0 = 32768, a1 = 32768, a2 = 32768;
+#pragma unroll
+  for (int i = 0; i < 5; ++i)
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      const uint32_t v = p[(i - 2) * ld + (j - 2)];
+      const int w = k[i * 5 + j];
+      a0 += w * (int)(v & 255u);
+      a1 += w * (int)((v >> 8) & 255u);
+      a2 += w * (int)(v >> 16);
+    }
+  return (uint32_t)min(255, a0 >> 16) | ((uint32_t)min(255, a1 >> 16) << 8) | ((uint32_t)min(255, a2 >> 16) << 16);
+}
+
+__global__ void __launch_bounds__(256) k_augment(const uint8_t* __restrict__ imgs, int H, int W,
+                                                 const int* __restrict__ img_index, const AugDesc* __restrict__ desc,
+                                                 const uint8_t* __restrict__ masks, int mh, int mw,
+                                                 const uint8_t* __restrict__ luts, const uint8_t* __restrict__ beta_tab,
+                                                 const int* __restrict__ bbox, uint8_t* __restrict__ out, int vec) {
+  __shared__ uint32_t p0[AUG_P0 * AUG_P0];
+  __shared__ uint32_t p1[AUG_P1 * AUG_P1];
+  __shared__ uint32_t obuf[AUG_T * AUG_T * 3 / 4];
+  __shared__ uint8_t lut_s[3 * 256];
+  __shared__ int mrow[AUG_P1], mcol[AUG_P1];
+  const int b = blockIdx.z, ty0 = blockIdx.y * AUG_T, tx0 = blockIdx.x * AUG_T, tid = threadIdx.x;
+  if (bbox) {  // only tiles meeting the region crop_square_resize copies: [max(x1,0), xe) x [max(y1,0), ye)
+    const CropGeo g = crop_geo(bbox + 4 * b, H, W);
+    if (g.s <= 0 || tx0 >= g.xe || ty0 >= g.ye || tx0 + AUG_T <= max(g.x1, 0) || ty0 + AUG_T <= max(g.y1, 0)) return;
+  }
+  const AugDesc* d = desc + b;
+  const uint32_t flags = d->flags;
+  const uint8_t* img = imgs + (size_t)img_index[b] * H * W * 3;
+
+  // stage 0 into p0; coordinates [t0 - 4, t0 + T + 4)
+  const bool sp = flags & 1u;
+  const uint32_t seed = d->sp_seed, thresh = d->sp_thresh;
+  for (int idx = tid; idx < AUG_P0 * AUG_P0; idx += 256) {
+    const int i = idx / AUG_P0, j = idx - i * AUG_P0;
+    const int y = reflect101(ty0 - 4 + i, H), x = reflect101(tx0 - 4 + j, W);
+    const uint8_t* s = img + ((size_t)y * W + x) * 3;
+    uint32_t v = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16);
+    if (sp) {
+      const uint32_t h1 = fmix32(seed ^ (((uint32_t)y * (uint32_t)W + (uint32_t)x) * 0x9E3779B9u));
+      if (h1 < thresh) v = (uint32_t)beta_tab[fmix32(h1 ^ 0x68bc21ebu) >> 24] * 0x010101u;
+    }
+    p0[idx] = v;
+  }
+  if (flags & 4u) {  // INTER_NEAREST row / column of the keep-mask for p1's coordinates
+    if (tid < AUG_P1)
+      mrow[tid] = min((int)floor(reflect101(ty0 - 2 + tid, H) * (1.0 / ((double)H / mh))), mh - 1);
+    else if (tid >= 64 && tid < 64 + AUG_P1)
+      mcol[tid - 64] = min((int)floor(reflect101(tx0 - 2 + tid - 64, W) * (1.0 / ((double)W / mw))), mw - 1);
+  }
+  if (flags & 16u)
+    for (int idx = tid; idx < 3 * 256; idx += 256) lut_s[idx] = luts[(size_t)b * 768 + idx];
+  __syncthreads();
+
+  // stages 1-2 into p1; coordinates [t0 - 2, t0 + T + 2).  An entry at c reads p0 around q = reflect101(c):
+  // rows q - 2 .. q + 2 relative to t0 - 4.  In the image q = c and the rows are c - t0 + 2 .. c - t0 + 6, within
+  // [0, T + 8).  c in {-2, -1} (t0 = 0): q in {1, 2}, rows 3 .. 8.  c in {n, n + 1} (n <= t0 + T + 1, t0 <= n - 1):
+  // q = 2n - 2 - c, rows 2n - c - t0 >= n - 1 - t0 >= 0 up to n + 4 - t0 <= T + 5.  Entries beyond n + 1 are
+  // never read by an in-image output and are left unset.
+  const uint8_t* mk = masks + (size_t)b * mh * mw;
+  for (int idx = tid; idx < AUG_P1 * AUG_P1; idx += 256) {
+    const int i = idx / AUG_P1, j = idx - i * AUG_P1;
+    const int cy = ty0 - 2 + i, cx = tx0 - 2 + j;
+    if (cy > H + 1 || cx > W + 1) continue;
+    const int by = min(max(reflect101(cy, H) - (ty0 - 4), 2), AUG_P0 - 3);
+    const int bx = min(max(reflect101(cx, W) - (tx0 - 4), 2), AUG_P0 - 3);
+    const uint32_t* c = p0 + by * AUG_P0 + bx;
+    uint32_t v = (flags & 2u) ? stencil5(c, AUG_P0, d->kA) : c[0];
+    if ((flags & 4u) && !mk[mrow[i] * mw + mcol[j]]) v = 0;
+    p1[idx] = v;
+  }
+  __syncthreads();
+
+  // stages 3-4 into the byte tile
+  uint8_t* ob = (uint8_t*)obuf;
+  for (int idx = tid; idx < AUG_T * AUG_T; idx += 256) {
+    const int oy = idx / AUG_T, ox = idx - oy * AUG_T;
+    if (ty0 + oy >= H || tx0 + ox >= W) continue;
+    const uint32_t* c = p1 + (oy + 2) * AUG_P1 + ox + 2;
+    const uint32_t v = (flags & 8u) ? stencil5(c, AUG_P1, d->kB) : c[0];
+    uint32_t c0 = v & 255u, c1 = (v >> 8) & 255u, c2 = v >> 16;
+    if (flags & 16u) {
+      c0 = lut_s[c0];
+      c1 = lut_s[256 + c1];
+      c2 = lut_s[512 + c2];
+    }
+    ob[idx * 3] = (uint8_t)c0;
+    ob[idx * 3 + 1] = (uint8_t)c1;
+    ob[idx * 3 + 2] = (uint8_t)c2;
+  }
+  __syncthreads();
+
+  // tile rows are wv * 3 contiguous bytes; as dwords when every row start is 4-byte aligned (vec)
+  const int hv = min(AUG_T, H - ty0), wv = min(AUG_T, W - tx0);
+  uint8_t* o = out + ((size_t)b * H * W + (size_t)ty0 * W + tx0) * 3;
+  if (vec) {
+    const int nd = wv * 3 / 4;
+    for (int idx = tid; idx < hv * nd; idx += 256) {
+      const int r = idx / nd, q = idx - r * nd;
+      ((uint32_t*)(o + (size_t)r * W * 3))[q] = obuf[r * (AUG_T * 3 / 4) + q];
+    }
+  } else {
+    const int nb = wv * 3;
+    for (int idx = tid; idx < hv * nb; idx += 256) {
+      const int r = idx / nb, q = idx - r * nb;
+      o[(size_t)r * W * 3 + q] = ob[r * AUG_T * 3 + q];
+    }
+  }
+}
+
 }  // namespace zp
 
 using namespace zp;
@@ -224,5 +373,25 @@ extern "C" int zp_pack_digits(const uint8_t* bits, int B, int nbits, int H, int 
   hipLaunchKernelGGL(k_pack_digits, dim3((HW + 255) / 256, nbits / s, B), dim3(256), 0, (hipStream_t)stream, bits, HW,
                      nbits, s, digits);
   ZP_LAUNCH_CHECK("zp_pack_digits");
+  return ZP_OK;
+}
+
+extern "C" int zp_augment(const uint8_t* imgs, int n_img, int H, int W, const int* img_index, const zp_aug_desc* desc,
+                          const uint8_t* masks, int mh, int mw, const uint8_t* luts, const uint8_t* beta_tab,
+                          const int* bbox, int B, uint8_t* out, void* stream) {
+  static_assert(sizeof(AugDesc) == sizeof(zp_aug_desc) && sizeof(zp_aug_desc) == 53 * 4, "zp_aug_desc layout");
+  ZP_CHECK_ARG(imgs && img_index && desc && masks && luts && beta_tab && out, "zp_augment: null pointer");
+  ZP_CHECK_ARG(n_img > 0 && B > 0 && B <= 65535, "zp_augment: bad n_img %d / B %d", n_img, B);
+  ZP_CHECK_ARG(H >= 8 && W >= 8 && H < (1 << 20) && W < (1 << 20),
+               "zp_augment: image %d x %d (the 5 x 5 stencils' reflected borders need H, W >= 8)", H, W);
+  ZP_CHECK_ARG(mh >= 1 && mw >= 1 && mh <= H && mw <= W, "zp_augment: dropout mask %d x %d for a %d x %d image", mh,
+               mw, H, W);
+  ZP_CHECK_ARG((long long)n_img * H * W * 3 < (1ll << 40) && (long long)B * H * W * 3 < (1ll << 40),
+               "zp_augment: image stack too large");
+  const int vec = (W * 3) % 4 == 0 && ((uintptr_t)out & 3) == 0;
+  hipLaunchKernelGGL(k_augment, dim3((W + AUG_T - 1) / AUG_T, (H + AUG_T - 1) / AUG_T, B), dim3(256), 0,
+                     (hipStream_t)stream, imgs, H, W, img_index, (const AugDesc*)desc, masks, mh, mw, luts, beta_tab,
+                     bbox, out, vec);
+  ZP_LAUNCH_CHECK("zp_augment");
   return ZP_OK;
 }
