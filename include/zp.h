@@ -35,6 +35,9 @@
  *   zp_augment         apply_augmentation (bop_dataset_pytorch.py:349-355): the imgaug colour chain of
  *                      GDR_Net_Augmentation.py:161-178 ahead of the is_train crop (:267-277)
  *   zp_adam            torch.optim.Adam step used by train_v6.py:268-269, 338
+ *   zp_render          the OpenGL GT renderer Binary_Code_GT_Generator/Render_GT_Color_Mesh_to_GT_Img
+ *                      (render_related_source/opengl_render.cpp:164-206, camera.hpp:29-59,
+ *                      shader_groundtruth.vs / .fs) driven by generate_training_labels_for_BOP_v2.py:77-85
  */
 #ifndef ZP_H_
 #define ZP_H_
@@ -531,6 +534,41 @@ typedef struct {
 int zp_augment(const uint8_t* imgs, int n_img, int H, int W, const int* img_index, const zp_aug_desc* desc,
                const uint8_t* masks, int mh, int mw, const uint8_t* luts, const uint8_t* beta_tab, const int* bbox,
                int B, uint8_t* out, void* stream);
+
+/* ---- GT renderer ------------------------------------------------------------------------
+ * B renders of one mesh (GT code images, depth, masks), replacing the reference's OpenGL program
+ * Render_GT_Color_Mesh_to_GT_Img: rendering_GT_once / render_3D_GT_Model
+ * (render_related_source/opengl_render.cpp:164-206: black clear, GL_LESS, no culling, no
+ * antialiasing), the projection of camera.hpp:29-59 (u = fx X / Z + cx, pixel centres at
+ * half-integers) and the pass-through shaders shader_groundtruth.vs / .fs.
+ *   verts f32 [nv][3], faces i32 [nf][3], face_bgr u8 [nf][3]: one colour per face in the byte order
+ *   zp_crop_gt reads (id = B << 16 | G << 8 | R); needed only when color is asked for.
+ *   Per render b: R f64 [B][9] row-major, t f64 [B][3], K f64 [B][4] = (fx, fy, cx, cy), as zp_pnp_ransac.
+ *   Outputs (each may be NULL): color u8 [B][H][W][3], depth f32 [B][H][W] (camera Z), mask u8
+ *   [B][H][W] (255 / 0), face_out i32 [B][H][W] (-1 = background); background is 0 in color, depth, mask.
+ * Semantics (tests/render_ref.py restates them in numpy; the outputs match it bit for bit):
+ *   vertex:   Xc = ((r0 x + r1 y) + r2 z) + tx in f64 (likewise Yc, Zc); u = (fx Xc) / Zc + cx,
+ *             v = (fy Yc) / Zc + cy; snapped to 1/256 px, xi = rint(256 u) (half to even), saturated
+ *             to +-2^28 so the edge functions fit int64.
+ *   triangle: discarded whole when any vertex has Zc < z_near or a NaN projection, when its snapped
+ *             area is 0, or when an index is outside [0, nv).  No back-face culling.
+ *   coverage: pixel (x, y) is sampled at (x + 1/2, y + 1/2); exact int64 edge functions; a sample
+ *             exactly on an edge belongs to the triangle for which that edge is a top or a left edge
+ *             in image coordinates, so triangles sharing an edge cover its samples exactly once.
+ *   depth:    q = (E12 (1/Z0) + E20 (1/Z1)) + E01 (1/Z2), invz = f32(q / A) (perspective-correct);
+ *             depth = f32(1 / f64(invz)).
+ *   visible:  the largest invz, ties to the lowest face index (GL_LESS under draw order), as one
+ *             64-bit key per pixel merged with an unsigned atomic max: independent of the order
+ *             triangles arrive in, bitwise reproducible.
+ *   colour:   the winning face's face_bgr (flat).
+ * Deviations from GL: no near / far clipping (the whole-triangle discard above; GT poses lie in
+ * front of the camera); flat per-face instead of interpolated per-vertex colour (equal on the GT
+ * meshes, whose faces are uniform); GL's choice for samples exactly on an edge is not pinned.
+ * H, W <= 32768; B * nv, B * nf, B * H * W < 2^31 - 1024.  ws: zp_render_ws_bytes bytes (-1: bad sizes). */
+long long zp_render_ws_bytes(int B, int nv, int nf, int H, int W);
+int zp_render(int B, const float* verts, int nv, const int* faces, int nf, const uint8_t* face_bgr,
+              const double* R, const double* t, const double* K, int H, int W, double z_near,
+              uint8_t* color, float* depth, uint8_t* mask, int* face_out, void* ws, void* stream);
 
 /* ---- optimizer ----------------------------------------------------------------------- */
 /* torch.optim.Adam (no weight decay, amsgrad off) over one flat f32 buffer; step >= 1 */
