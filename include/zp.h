@@ -197,10 +197,12 @@ long long zp_conv2d_split_ws(const zp_conv_args* a);
  * = the 256 x 256 two-plane tile on 32x32x16 MFMAs (default 0); key 19 = the ring depth (2, 3, 4) of
  * the register-pipelined two-plane 64-channel tile (default 2); key 20 = persistent workgroups per CU
  * of the two-plane stem (1 or 2, default 1); key 21 = the wide strip tile's next-step pixel fragments
- * read before the step's barrier (1, default) or after it (0).  Keys 7, 10 and 13-21 hold -1 until
- * set: the environment (ZP_CONV3_STRIP, ZP_CONV3W, ZP_CONV3W_ACC, ZP_CONV3W_TP128, ZP_BN_FUSED,
- * ZP_CONV3_SUBINT, ZP_CONV3W_SUBINT, ZP_CONV3W_MF32, ZP_CONV3_PIPE_ST, ZP_STEM_WGS, ZP_CONV3W_PFB) or
- * the default then decides.  Returns the previous value, -1 for an unknown key. */
+ * read before the step's barrier (1, default) or after it (0); key 22 = the wide strip tile's two
+ * wave groups half a K step apart (the ping-pong K loop: 1 on, 0 off; the default decides per
+ * geometry; launches that are not one-sub strip launches keep the lock-step loop).  Keys 7, 10 and
+ * 13-22 hold -1 until set: the environment (ZP_CONV3_STRIP, ZP_CONV3W, ZP_CONV3W_ACC, ZP_CONV3W_TP128,
+ * ZP_BN_FUSED, ZP_CONV3_SUBINT, ZP_CONV3W_SUBINT, ZP_CONV3W_MF32, ZP_CONV3_PIPE_ST, ZP_STEM_WGS,
+ * ZP_CONV3W_PFB, ZP_CONV3W_PP) or the default then decides.  Returns the previous value, -1 for an unknown key. */
 int zp_conv_tuning(int key, int value);
 
 /* Fused 1x1 head (the reference's conv_1x1_4 over torch.cat([x, x_128]) and the mask / code split,

@@ -45,6 +45,8 @@ def main():
     ap.add_argument("--mf32", default="-1", help="zp_conv_tuning key 18 values to A/B (k_conv3w on 32x32x16 MFMAs: 0, 1)")
     ap.add_argument("--pfb", default="-1", help="zp_conv_tuning key 21 values to A/B (k_conv3w strip tile: next-step "
                     "pixel fragments read before the barrier: 0, 1)")
+    ap.add_argument("--pp", default="-1", help="zp_conv_tuning key 22 values to A/B (k_conv3w strip tile: the two "
+                    "wave groups half a K step apart: 0, 1)")
     ap.add_argument("--graph", action="store_true", help="time hipGraph replays of the iters launches (no host "
                     "launch overhead: the bs = 1 launches are shorter than their eager enqueue)")
     ap.add_argument("--wsubint", default="-1", help="zp_conv_tuning key 17 values to A/B (k_conv3w ConvT phases "
@@ -100,11 +102,12 @@ def main():
     wsis = [int(m) for m in a.wsubint.split(",")]
     mfs = [int(m) for m in a.mf32.split(",")]
     pfbs = [int(m) for m in a.pfb.split(",")]
+    pps = [int(m) for m in a.pp.split(",")]
     first = {}
     import itertools
     for r in range(a.rounds):
-        for f0, mb, sm, wd, sk, ac, tq, si, ws, mf, pb in itertools.product(flags, mbs, strips, wides, sks, accs, t128,
-                                                                             sis, wsis, mfs, pfbs):
+        for f0, mb, sm, wd, sk, ac, tq, si, ws, mf, pb, pp in itertools.product(flags, mbs, strips, wides, sks, accs,
+                                                                                 t128, sis, wsis, mfs, pfbs, pps):
             L.lib.zp_conv_tuning(1, f0)
             L.lib.zp_conv_tuning(8, mb)
             L.lib.zp_conv_tuning(7, sm)
@@ -116,7 +119,8 @@ def main():
             L.lib.zp_conv_tuning(17, ws)
             L.lib.zp_conv_tuning(18, mf)
             L.lib.zp_conv_tuning(21, pb)
-            f = (f0, mb, sm, wd, sk, ac, tq, si, ws, mf, pb)
+            L.lib.zp_conv_tuning(22, pp)
+            f = (f0, mb, sm, wd, sk, ac, tq, si, ws, mf, pb, pp)
             for name, eng, unit, x, y, fl in setups:
                 def run1():
                     if hasattr(unit, "outs"):
@@ -170,10 +174,13 @@ def main():
     L.lib.zp_conv_tuning(17, -1)
     L.lib.zp_conv_tuning(18, -1)
     L.lib.zp_conv_tuning(21, -1)
+    L.lib.zp_conv_tuning(22, -1)
     for (name, f), v in sorted(res.items()):
         fl = [s[5] for s in setups if s[0] == name][0]
         us = min(v)
-        print(f"{name:8s} flags {f[0]:6d} minblocks {f[1]:4d} strip {f[2]:2d} wide {f[3]:2d} splitk {f[4]} acc {f[5]:2d} tp128 {f[6]:2d} subint {f[7]:2d} wsubint {f[8]:2d} mf32 {f[9]:2d} pfb {f[10]:2d}: {us:9.1f} us  {fl / us * 1e-6:7.1f} TFLOP/s  ({fl / us * 1e-6 / (2516.6 / (6 if a.form == 'x3' else 3)):.3f} of the {a.form} ceiling)")
+        vs = sorted(v)
+        med = vs[len(vs) // 2]
+        print(f"{name:8s} flags {f[0]:6d} minblocks {f[1]:4d} strip {f[2]:2d} wide {f[3]:2d} splitk {f[4]} acc {f[5]:2d} tp128 {f[6]:2d} subint {f[7]:2d} wsubint {f[8]:2d} mf32 {f[9]:2d} pfb {f[10]:2d} pp {f[11]:2d}: min {us:9.1f} us (median {med:9.1f}, max {vs[-1]:9.1f})  {fl / us * 1e-6:7.1f} TFLOP/s  ({fl / us * 1e-6 / (2516.6 / (6 if a.form == 'x3' else 3)):.3f} of the {a.form} ceiling)")
 
 
 if __name__ == "__main__":

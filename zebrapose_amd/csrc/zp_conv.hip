@@ -2334,6 +2334,7 @@ extern "C" int zp_conv_tuning(int key, int value) {
     case 19: return conv3_pipe_st_mode(value);
     case 20: return stem_wgs_mode(value);
     case 21: return conv3w_pfb_mode(value);
+    case 22: return conv3w_pp_mode(value);
     default: return -1;
   }
   const int old = *g;

@@ -31,6 +31,13 @@
 // every fragment read is a lane-linear conflict-free ds_read_b128.  2-stage ring of 64 KB: the DMA
 // of step k + 1 is issued at the top of step k into the buffer step k - 1 read (every wave passed
 // the barrier that ended step k - 1) and has the whole step to land.
+// Ping-pong (template PP, zp_conv_tuning key 22, round 7): the strip tile with its two wave groups
+// (cout halves; waves w and w + 4 share a SIMD) half a K step apart, so that one group's step start
+// and barrier wait fall inside the other's MFMA blocks.  LDS: the SAME two 32 KB weight stages and
+// 2-stage strip ring (144 KB) -- neither a ring of half-stages nor a per-geometry strip ring was
+// needed.  The third stage a lagging group would need under whole-stage DMA is avoided by moving the
+// lagging group's barrier to mid-step and staging the two weight tiles it reads after that barrier
+// (14, 15) one barrier interval later than the other fourteen; the argument is at the K loop.
 // Epilogue: v_permlane16_swap pairs the lane groups of cout blocks (i, i + 1) so that a lane holds
 // 8 consecutive output channels of one pixel: 16 B stores per lane and plane (k_conv3 stores 8 B),
 // 16 B residual loads.
@@ -84,7 +91,7 @@ __device__ unsigned long long zp_stamp_buf[ZP_STAMP_WAVES * 8];
 #endif
 
 template <int ABL, int DM, bool HEAD, bool SGB = false, bool PF = false, bool BF = false, bool STR = false,
-          int NUM = ACC_FLUSH, int TPX = 256, bool PFB = false>
+          int NUM = ACC_FLUSH, int TPX = 256, bool PFB = false, bool PP = false>
 __global__ void __launch_bounds__(512) k_conv3w(const zp_conv_args A, const conv_taps TG, const int flags,
                                                 const zp_head_args H, float* __restrict__ ws, const int nsplit) {
   constexpr int NPL = 2;
@@ -102,6 +109,8 @@ __global__ void __launch_bounds__(512) k_conv3w(const zp_conv_args A, const conv
   // strip, or the next group's, issued in the group's first step and complete and visible since the
   // barrier of its second.  One sub, no split-K (conv3w_launch checks)
   static_assert(!PFB || (STR && !P2 && NUM == ACC_FLUSH && TPX == 256), "pixel-fragment prefetch: the strip tile");
+  static_assert(!PP || (STR && !PFB && NUM == ACC_FLUSH && TPX == 256 && ABL == 0 && DM == 1 && !SGB && !PF && !BF),
+                "ping-pong: the flushed strip tile, default DMA order");
   constexpr int NTW = TC / 16, NT = (TC + TP) / 16;  // weight tiles / all tiles per plane (16 rows each)
   constexpr int UNITS = NPL * NT;                    // 1 KB DMA units per stage
   constexpr int WC = 8, WP = TP / 64;                // per wave: 8 cout blocks x 4 (TP 128: 2) pixel blocks
@@ -316,6 +325,42 @@ __global__ void __launch_bounds__(512) k_conv3w(const zp_conv_args A, const conv
       ++g_cb;
     }
   };
+  // PP: the weight DMA of one barrier interval (see the schedule note at the K loop).  Interval k
+  // stages this wave's cout-half-0 tile (wid) and, on waves 0 .. 5, its cout-half-1 tile (8 + wid) of
+  // step k + 1 into stage (k + 1) & 1; waves 6 and 7 stage their cout-half-1 tiles (14, 15: the ones
+  // group B reads after its mid-step barrier) of step k into stage k & 1.  Every wave calls it with
+  // the same k, so the walk (prep) is the same in every wave.  A piece past the slice is out of range:
+  // it stores ZEROS (as the padding pieces do), so it may only target tiles nobody reads any more --
+  // true of step nK's tiles; interval 0 therefore re-stages step 0's late tiles (the prologue's, the
+  // same bytes, read after b_0) instead of an out-of-range piece over them
+  const bool grpB = PP && wc == 1;
+  int pp_k = 0, pp_kcur = w_koff;  // the interval to issue; the weight K offset of step pp_k
+  auto pp_issue = [&]() {
+    DmaStep d;
+    prep(d);
+    const bool late = wid >= 6;
+    const bool nxt = pp_k + 1 < nK, cur = pp_k < nK;
+    const int st1 = (pp_k + 1) & 1;
+    const unsigned va = nxt ? ubase[0] : 0x80000000u;
+    const unsigned vb = (late ? cur : nxt) ? ubase[1] : 0x80000000u;
+    const int sb = late ? st1 ^ 1 : st1, kb = late ? pp_kcur : d.koff;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int pl = 0; pl < NPL; ++pl) {
+      auto* da = (__attribute__((address_space(3))) void*)&lds[(st1 * ASTG + pl * APL + wid) * 64];
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, da, 16, va, pl * psw_b + d.koff, 0, 0);
+    }
+#pragma unroll
+    for (int pl = 0; pl < NPL; ++pl) {
+      auto* db = (__attribute__((address_space(3))) void*)&lds[(sb * ASTG + pl * APL + wid + 8) * 64];
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, db, 16, vb, pl * psw_b + kb, 0, 0);
+    }
+#else
+    (void)va; (void)vb; (void)sb; (void)kb; (void)st1;
+#endif
+    pp_kcur = d.koff;
+    ++pp_k;
+  };
   // STR: the step being computed reads strip stage r_gs at tap column r_txi
   int r_txi = 0, r_gs = 0;
   const unsigned sl0 = lds_addr(lds) + (unsigned)(2 * ASTG) * 1024u + (unsigned)(lane >> 4) * 256u;
@@ -407,8 +452,8 @@ __global__ void __launch_bounds__(512) k_conv3w(const zp_conv_args A, const conv
     // step which read it): one piece per cout block, after that block's correction MFMAs, so that
     // the issue cost (~60 cycles per piece beside MFMAs) is spread over the step
     DmaStep dn;
-    prep(dn);
-    if (!more) {  // no next step: every piece's offset out of the buffers' range (the unit returns, stores nothing)
+    if constexpr (!PP) prep(dn);
+    if (!PP && !more) {  // no next step: every piece's offset out of the buffers' range (the unit returns, stores nothing)
 #pragma unroll
       for (int k = 0; k < TPW; ++k) dn.voff[k] = 0x80000000u;
       dn.koff = 0;
@@ -449,6 +494,18 @@ __global__ void __launch_bounds__(512) k_conv3w(const zp_conv_args A, const conv
     f32x4 c2p[WP];  // NUM 0 / 2: the previous cout block's per-step sums (flushed one block later)
     static_for<WC>([&](auto i_c) {
       constexpr int i = decltype(i_c)::value;
+      if constexpr (PP && i == WC / 2) {
+        // group B's barrier of the step, before block 4 prefetches tile 14 (a late tile).  The reads of
+        // blocks 4 and 5 are in flight: complete them first, so that no fragment read is outstanding
+        // at a barrier (the DMA after it overwrites only what every wave has finished reading)
+        if (grpB) {
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          if (strip_now) vm_wait<4>();
+          else vm_wait<0>();
+          wbarrier();
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
       if constexpr (i + 2 < WC) {
         static_for<NPL>([&](auto p_c) {
           constexpr int p = decltype(p_c)::value;
@@ -492,7 +549,13 @@ __global__ void __launch_bounds__(512) k_conv3w(const zp_conv_args A, const conv
           else MT::mma(c2[j], af[i % 3][0], bf[1][j]);
         }
       }
-      if constexpr (i < DM && !abl_dma)  // (no branch: after the last step the pieces are out of range -> no-ops)
+      if constexpr (PP) {  // the interval's weight pieces: group A in block 0, group B right after its barrier
+        if constexpr (i == 0) {
+          if (!grpB) pp_issue();
+        } else if constexpr (i == WC / 2) {
+          if (grpB && more) pp_issue();  // (interval nK has nothing to stage)
+        }
+      } else if constexpr (i < DM && !abl_dma)  // (no branch: after the last step the pieces are out of range -> no-ops)
         static_for<NPC / DM>([&](auto q_c) {
           constexpr int q = i * (NPC / DM) + decltype(q_c)::value;
           piece(std::integral_constant<int, BF ? (q + NPC / 2) % NPC : q>{}, s ^ 1, dn);
@@ -550,6 +613,9 @@ __global__ void __launch_bounds__(512) k_conv3w(const zp_conv_args A, const conv
   wbarrier();
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (PFB) load_bf(r_gs, r_txi);
+  if constexpr (PP) {
+    if (grpB) pp_issue();  // interval 0's pieces (group A issues them in block 0 of step 0)
+  }
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
   if (flags & 65536) {  // static priority for the second-dispatched half (MI355X_MICROARCH.md item 4)
@@ -558,11 +624,13 @@ __global__ void __launch_bounds__(512) k_conv3w(const zp_conv_args A, const conv
   // STR: a step that issued the next group's strip waits for its own per-step pieces only (issued
   // before the strip's 4 .. 6: vmcnt counts in order); the strip lands by the next step's full wait
   auto end_step = [&](const bool sn) {
-    if (STR && sn && nx > 1) vm_wait<4>();  // (one-column groups: the strip is read at the next step)
-    else vm_wait<0>();
-    asm volatile("" ::"v"(pf_sink));  // the prefetch's (discarded) value: consumed after the wait
-    ZP_STAMP_AT(2);
-    if constexpr (!abl_bar) wbarrier();
+    if (!grpB) {  // (PP: group B's wait and barrier of the step are before its block 4)
+      if (STR && sn && nx > 1) vm_wait<4>();  // (one-column groups: the strip is read at the next step)
+      else vm_wait<0>();
+      asm volatile("" ::"v"(pf_sink));  // the prefetch's (discarded) value: consumed after the wait
+      ZP_STAMP_AT(2);
+      if constexpr (!abl_bar) wbarrier();
+    }
     __builtin_amdgcn_sched_barrier(0);
     ZP_STAMP_AT(3);
     if constexpr (STR) {
@@ -585,6 +653,35 @@ __global__ void __launch_bounds__(512) k_conv3w(const zp_conv_args A, const conv
   ZP_STAMP_AT(-1);
   st_loop0 = st_t;
 #endif
+  // PP (zp_conv_tuning key 22): the ping-pong schedule.  Group A = the cout-half-0 waves 0 .. 3, group
+  // B = waves 4 .. 7; waves w and w + 4 share a SIMD.  Both run the same step code in the same K
+  // order; the only difference is WHERE in the step a wave executes the step's one s_barrier: A
+  // after block 7 (as today), B before block 4.  B therefore waits half a step at the first barrier
+  // and from then on runs half a step behind A: when A starts a step (fragment reads, their
+  // latency), B is in blocks 4 .. 7 with its fragments in registers, and the other way round.
+  //   Barrier count.  Barriers b_0 .. b_nK follow the prologue's.  Every wave runs nK steps (nK is
+  // workgroup-uniform: kernel arguments and blockIdx only) and every step executes exactly one
+  // barrier, at a place fixed by wc alone -- no barrier sits under `more`, `strip_now`, the tap
+  // walk, the step parity (an odd nK leaves the loop after a whole step) or the split-K slice; then
+  // every wave executes b_nK below.  So each wave executes nK + 1 barriers on every path, and the
+  // HEAD tail's two __syncthreads follow b_nK in all of them.
+  //   Interval I_k = (b_{k-1}, b_k), b_{-1} the prologue's: A computes step k; B computes blocks
+  // 4 .. 7 of step k - 1, then blocks 0 .. 3 of step k (and has issued the reads of its blocks 4, 5:
+  // tiles 12, 13).  Stage k & 1 holds step k.  What is read in which interval:
+  //     A's tiles 0 .. 7 and B's "early" tiles 8 .. 13 of step k: in I_k;
+  //     B's "late" tiles 14, 15 of step k: in I_{k+1} (block 4 prefetches tile 14 after b_k);
+  //     the strip of a tap-row group: from A's first step of the group to B's last (pixel
+  //     fragments are read at a step's start only).
+  // What pp_issue stages in I_k: tiles 0 .. 13 of step k + 1 into stage (k + 1) & 1 -- last read in
+  // I_{k-1} (step k - 1), every such read waited for before its wave reached b_{k-1} -- and tiles
+  // 14, 15 of step k into stage k & 1, last read in I_{k-1} (step k - 2's).  Each wave waits for its
+  // own pieces of I_k by a counted vmcnt before b_k (a strip issued in this step may stay in flight:
+  // vmcnt counts in order, the strip's 4 .. 6 pieces come after the weights'), so they are visible
+  // after b_k, where their first reads are.  Hence two weight stages suffice: the third stage a
+  // lagging group would need with whole-stage DMA is replaced by staging the two late tiles one
+  // interval later.  A strip is issued in a group's first step (A: I_k, k = g nx; B: the same
+  // interval, later) into the stage last read at the start of step k - 1 (in I_{k-1}), and is waited
+  // for in full before b_{k+1}; its first read is after b_{k+nx-1}, nx >= 2 (the launcher checks).
   for (int ks = 0; ks < nK; ks += 2) {
     // step ks on buffer 0, issuing the DMA of step ks + 1 into buffer 1
     const bool sn0 = STR && r_txi == 0 && ks + nx < nK;
@@ -594,6 +691,14 @@ __global__ void __launch_bounds__(512) k_conv3w(const zp_conv_args A, const conv
     const bool sn1 = STR && r_txi == 0 && ks + 1 + nx < nK;
     step(I1{}, ks + 2 < nK, sn1);
     end_step(sn1);
+  }
+  if constexpr (PP) {
+    // barrier nK of the schedule note: group A has finished step nK - 1, group B finishes its second
+    // half here (block 7 waited for its last fragment read; nothing it issued since its barrier
+    // nK - 1 stores to LDS).  Past it no wave reads the rings: the HEAD tail may restage the LDS
+    if (grpB) vm_wait<0>();
+    wbarrier();
+    __builtin_amdgcn_sched_barrier(0);
   }
 #ifdef ZP_STAMP
   if constexpr (STAMP) {
@@ -1034,6 +1139,33 @@ static bool conv3w_pfb_on() {
   static const int env = getenv("ZP_CONV3W_PFB") ? atoi(getenv("ZP_CONV3W_PFB")) : 1;
   return (g_conv3w_pfb >= 0 ? g_conv3w_pfb : env) != 0;
 }
+// zp_conv_tuning key 22: the ping-pong K loop of the flushed strip tile (PP: the two wave groups half a
+// step apart; one-sub strip launches, i.e. stride-1 convs with >= 2 tap columns -- every other launch
+// keeps the loop above whatever the key says).  0: off, 1: on, -1: ZP_CONV3W_PP or the per-geometry
+// default of conv3w_pp_default
+static int g_conv3w_pp = -1;
+int conv3w_pp_mode(int v) {
+  const int old = g_conv3w_pp;
+  g_conv3w_pp = v;
+  return old;
+}
+// the default per launch, each from its own A/B (tools/conv3_ab.py --pp 0,1, profiles/r07_pingpong_ab.md)
+static bool conv3w_pp_default(const zp_conv_args& a, int ns, bool head) {
+  // bs 32, 5 interleaved rounds, min .. max of each side (profiles/r07_pingpong_ab.md): layer5's 512 -> 512
+  // d4 at 32 x 32 337.7 .. 431.8 -> 329.8 .. 335.6 us, up1's 3x3 at 64 x 64 363.5 .. 418.1 -> 355.0 .. 360.8
+  // us.  up2's 3x3 at 128 x 128 (1448.9 .. 1575.1 -> 1441.8 .. 1522.9 us) is inside its own spread as a
+  // lone launch; it and the fused up2-conv + head launch of the same geometry are decided by the whole
+  // step, where they are the only difference between "on at GW <= 64" (9.314 .. 9.334 ms) and "on
+  // everywhere" (9.235 .. 9.245 ms; parent 9.357 .. 9.376 ms): on
+  (void)a; (void)ns; (void)head;
+  return true;
+}
+static bool conv3w_pp_on(const zp_conv_args& a, const conv_taps& tg, bool str, int ns, bool head) {
+  static const int env = getenv("ZP_CONV3W_PP") ? atoi(getenv("ZP_CONV3W_PP")) : -1;
+  if (!str || a.nsub != 1 || tg.nx[0] < 2) return false;
+  const int v = g_conv3w_pp >= 0 ? g_conv3w_pp : env;
+  return v < 0 ? conv3w_pp_default(a, ns, head) : v != 0;
+}
 void conv3w_launch(const zp_conv_args& a0, const conv_taps& tg0, hipStream_t st, int fl, float* ws, int ns) {
   // several sub-problems (the ConvT phases: 1 / 2 / 2 / 4 taps): dispatched longest first (the
   // dispatcher walks blockIdx.z slowest, so the 4-tap phase's workgroups start first and the
@@ -1108,7 +1240,9 @@ void conv3w_launch(const zp_conv_args& a0, const conv_taps& tg0, hipStream_t st,
   } else if (acc == ACC_FS) {  // the flushed form on the 2^11 scale
     if (str) hipLaunchKernelGGL((k_conv3w<0, 1, false, false, false, false, true, ACC_FS>), grid, dim3(512), 0, st, a, tg, fl, H, ws, ns);
     else hipLaunchKernelGGL((k_conv3w<0, 1, false, false, false, false, false, ACC_FS>), grid, dim3(512), 0, st, a, tg, fl, H, ws, ns);
-  } else if (str && ns == 1 && a.nsub == 1 && tg.nx[0] == 3 && conv3w_pfb_on())  // (key 21: pixel-fragment prefetch)
+  } else if (conv3w_pp_on(a, tg, str, ns, false))  // (key 22: the ping-pong K loop)
+    hipLaunchKernelGGL((k_conv3w<0, 1, false, false, false, false, true, ACC_FLUSH, 256, false, true>), grid, dim3(512), 0, st, a, tg, fl, H, ws, ns);
+  else if (str && ns == 1 && a.nsub == 1 && tg.nx[0] == 3 && conv3w_pfb_on())  // (key 21: pixel-fragment prefetch)
     hipLaunchKernelGGL((k_conv3w<0, 1, false, false, false, false, true, ACC_FLUSH, 256, true>), grid, dim3(512), 0, st, a, tg, fl, H, ws, ns);
   else if (str)  // the default: k_conv3's flushed correction accumulator (bit-identical to k_conv3<h2>)
     hipLaunchKernelGGL((k_conv3w<0, 1, false, false, false, false, true>), grid, dim3(512), 0, st, a, tg, fl, H, ws, ns);
@@ -1126,6 +1260,8 @@ void conv3w_head_launch(const zp_conv_args& a, const conv_taps& tg, const zp_hea
   } else if (acc == ACC_FS) {
     if (str) hipLaunchKernelGGL((k_conv3w<0, 1, true, false, false, false, true, ACC_FS>), grid, dim3(512), 0, st, a, tg, fl, h, nullptr, 1);
     else hipLaunchKernelGGL((k_conv3w<0, 1, true, false, false, false, false, ACC_FS>), grid, dim3(512), 0, st, a, tg, fl, h, nullptr, 1);
+  } else if (conv3w_pp_on(a, tg, str, 1, true)) {
+    hipLaunchKernelGGL((k_conv3w<0, 1, true, false, false, false, true, ACC_FLUSH, 256, false, true>), grid, dim3(512), 0, st, a, tg, fl, h, nullptr, 1);
   } else if (str) {
     hipLaunchKernelGGL((k_conv3w<0, 1, true, false, false, false, true>), grid, dim3(512), 0, st, a, tg, fl, h, nullptr, 1);
   } else {
