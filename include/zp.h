@@ -38,6 +38,9 @@
  *   zp_render          the OpenGL GT renderer Binary_Code_GT_Generator/Render_GT_Color_Mesh_to_GT_Img
  *                      (render_related_source/opengl_render.cpp:164-206, camera.hpp:29-59,
  *                      shader_groundtruth.vs / .fs) driven by generate_training_labels_for_BOP_v2.py:77-85
+ *   zp_mesh_code       the offline coder Binary_Code_GT_Generator/Generate_Mesh_with_GT_Color
+ *                      (Generate_Mesh_with_GT_Color.cpp:61-218 balanced 2-means split, :322-455 vertex /
+ *                      face ids and the class -> 3D-point LUT), binary splits only
  */
 #ifndef ZP_H_
 #define ZP_H_
@@ -571,6 +574,47 @@ long long zp_render_ws_bytes(int B, int nv, int nf, int H, int W);
 int zp_render(int B, const float* verts, int nv, const int* faces, int nf, const uint8_t* face_bgr,
               const double* R, const double* t, const double* K, int H, int W, double z_near,
               uint8_t* color, float* depth, uint8_t* mask, int* face_out, void* ws, void* stream);
+
+/* ---- mesh coder --------------------------------------------------------------------------
+ * Surface codes of a raw triangle mesh: per-vertex class id, per-face class id and the class ->
+ * 3D-point LUT, replacing the reference's offline tool Generate_Mesh_with_GT_Color (PCL + OpenCV):
+ * `bits` levels of a balanced 2-means split of the vertices (Generate_Mesh_with_GT_Color.cpp:61-218),
+ * ids with the first split as the MSB (:322-353), the face rule (:356-393) and the LUT (:396-455).
+ * Binary splits only (the reference's balancing and bit assembly are 2-way; divide_number > 2 is
+ * not supported).  OpenCV's k-means++ draws cannot be reproduced, so the semantics are restated in
+ * exact integer arithmetic (tests/meshcode_ref.py restates them in numpy; the outputs match it bit
+ * for bit and do not depend on the order of any summation):
+ *   grid:     q = rint(f64(v) * 2^grid_log2) per coordinate, saturated to +-(2^19 - 1).  The host
+ *             passes the largest grid_log2 for which no coordinate saturates.  From here on all
+ *             clustering arithmetic is int64: |delta| <= 2^20, d^2 < 2^42, sums over <= 2^21 vertices.
+ *   level l:  (l = 0 .. bits - 1) 2^l groups, the root group being all vertices; a group's vertices
+ *             are taken in ascending vertex index wherever an order matters; n >= 2^(bits - l) each.
+ *   2-means:  per group, `attempts` tries.  Seeds from one uint32 draw r per (attempt, group),
+ *             draws[attempt][(2^l - 1) + g]: c0 = the vertex at rank (r * n) >> 32, c1 = the group's
+ *             vertex with the largest d^2 to c0 (ties: lowest index).  Up to `iterations` Lloyd steps:
+ *             label = nearer centre (ties: class 0); each non-empty class's centre becomes
+ *             floor((2 S + n_j) / (2 n_j)) per axis, an empty class keeps its centre; the group
+ *             stops after the step in which the larger of the two centre shifts^2 is <= eps2_q
+ *             (= floor((eps * 2^grid_log2)^2)).  Compactness = sum of d^2 to the own centre under one
+ *             more labelling; the attempt with the lowest compactness wins (ties: lowest attempt).
+ *   balance:  with the winning centres' labels and m = floor(n / 2): a class with more than m
+ *             vertices keeps the m with the largest d^2 to the OTHER centre (ties: lower index), the
+ *             rest change class.  Children of group g: 2g (bit 0) and 2g + 1 (bit 1).
+ *   ids:      vertex id = sum_l bit_l * 2^(bits - 1 - l); face id, from its vertices' ids i0, i1, i2:
+ *             i0 if i0 == i1 or i0 == i2, else i1 if i1 == i2, else i0.
+ *   LUT:      per class the f64 mean of the f32 positions of the three vertices of each of its
+ *             faces (with multiplicity), summed in ascending face index, vertex 0, 1, 2 as single
+ *             IEEE additions; a class without a face is NaN (bits 0x7FF8000000000000).
+ * verts f32 [nv][3] (finite), faces i32 [nf][3] (indices in [0, nv); an index outside is read as the
+ * nearest valid one), draws u32 [attempts][2^bits - 1] (device memory, like every pointer here);
+ * outputs vertex_ids i32 [nv], face_ids i32 [nf], lut f64 [2^bits][3].
+ * 1 <= bits <= 16, 2^bits <= nv <= 2^21, 1 <= nf <= 2^24, 1 <= attempts <= 64, 1 <= iterations <= 1000,
+ * |grid_log2| <= 40, eps2_q >= 0; anything else, or a NULL pointer, is ZP_ERR_ARG before any device
+ * call.  ws: zp_mesh_code_ws_bytes bytes (-1: bad sizes). */
+long long zp_mesh_code_ws_bytes(int nv, int nf, int bits);
+int zp_mesh_code(const float* verts, int nv, const int* faces, int nf, int bits, int attempts, int iterations,
+                 int grid_log2, long long eps2_q, const uint32_t* draws, int* vertex_ids, int* face_ids, double* lut,
+                 void* ws, void* stream);
 
 /* ---- optimizer ----------------------------------------------------------------------- */
 /* torch.optim.Adam (no weight decay, amsgrad off) over one flat f32 buffer; step >= 1 */

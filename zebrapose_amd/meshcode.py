@@ -1,0 +1,147 @@
+"""Surface codes of a raw mesh on the device (``zp_mesh_code``, csrc/zp_meshcode.hip).
+
+The reference codes a mesh offline with the C++ tool
+Binary_Code_GT_Generator/Generate_Mesh_with_GT_Color (PCL + OpenCV): a recursive balanced 2-means
+split of the vertices, ``bits`` levels deep, gives every vertex a class id; faces take an id from
+their vertices, and the class -> 3D-point LUT is the mean of each class's face vertices.  Its
+outputs are the GT-colour mesh ``models_GT_color/obj_*.ply`` that ``MeshRenderer`` draws and the
+LUT ``Class_CorresPoint*.txt`` that ``Decoder`` reads.  ``encode_mesh`` produces both from a raw
+mesh on the device.  OpenCV's k-means++ draws cannot be reproduced, so the split is restated in
+exact integer arithmetic: the semantics are in include/zp.h (zp_mesh_code) and, as numpy, in
+tests/meshcode_ref.py; results are bit-for-bit reproducible for a given seed.  Binary splits only
+(the reference's ``divide_number`` is fixed at 2).  Dataset walking and OBJ input are out of scope.
+"""
+from __future__ import annotations
+
+from fractions import Fraction
+
+import numpy as np
+
+from .render import MeshRenderer, face_bgr_from_ids
+
+_SAT = (1 << 19) - 1
+
+
+def grid_log2(vertices):
+    """The largest k in [-40, 40] for which rint(|v| * 2^k) stays within 2^19 - 1 for every coordinate."""
+    m = float(np.abs(np.asarray(vertices, dtype=np.float32).astype(np.float64)).max())
+    for k in range(40, -41, -1):
+        if np.rint(np.ldexp(m, k)) <= _SAT:
+            return k
+    raise ValueError(f"mesh extent {m:g} is too large for the coder's grid")
+
+
+def eps_to_grid(eps, k):
+    """floor((eps * 2^k)^2) in exact arithmetic, capped at 2^62 (no centre shift^2 reaches 2^42)."""
+    eps = float(eps)
+    if not np.isfinite(eps) or eps < 0:
+        raise ValueError("eps must be finite and >= 0")
+    return min(int((Fraction(eps) * Fraction(2) ** k) ** 2), 1 << 62)
+
+
+class MeshCode:
+    """Result of ``encode_mesh``: ``vertex_ids`` i32 [nv], ``face_ids`` i32 [nf] and ``lut`` f64
+    [2^bits, 3] (NaN rows: classes without a face) as device tensors, ``bits``, the mesh
+    (``vertices`` f32 [nv, 3], ``faces`` i32 [nf, 3], numpy) and the ``draws`` u32
+    [attempts, 2^bits - 1] that seeded the split."""
+
+    def __init__(self, vertices, faces, bits, vertex_ids, face_ids, lut, draws):
+        self.vertices, self.faces, self.bits = vertices, faces, bits
+        self.vertex_ids, self.face_ids, self.lut, self.draws = vertex_ids, face_ids, lut, draws
+
+    def renderer(self, device=None):
+        """A ``MeshRenderer`` whose colours carry the face ids (what the label generator draws)."""
+        return MeshRenderer.from_class_ids(self.vertices, self.faces, self.face_ids.cpu().numpy(),
+                                           device=self.face_ids.device if device is None else device)
+
+    def decoder(self, ignore_bit=0, device=None):
+        from .decode import Decoder
+        return Decoder([self.lut.cpu().numpy()], device=self.lut.device if device is None else device,
+                       ignore_bit=ignore_bit)
+
+    def write_lut_file(self, path):
+        """The generator's ``Class_CorresPoint*.txt`` (Generate_Mesh_with_GT_Color.cpp:616-624):
+        ``"N 2 L"``, then ``"id x y z"`` per class with ``%g`` numbers as the C++ stream prints them;
+        a class without a face is written as ``nan``."""
+        lut = self.lut.cpu().numpy()
+        with open(path, "w") as f:
+            f.write(f"{len(lut)} 2 {self.bits}\n")
+            for i, (x, y, z) in enumerate(lut):
+                f.write("%d %s %s %s\n" % (i, *("nan" if v != v else "%g" % v for v in (x, y, z))))
+
+    def write_ply(self, path):
+        """The GT-colour mesh as create_mesh_with_labeled_color builds it
+        (Generate_Mesh_with_GT_Color.cpp:471-538), binary little-endian: walking the faces in order, a
+        vertex's first use keeps its index and every later use appends a duplicate, so that all three
+        vertices of a face carry the face's colour R = id & 255, G = (id >> 8) & 255, B = id >> 16.
+        A vertex no face uses keeps its position (the reference leaves it at the origin), black."""
+        v, faces = self.vertices, self.faces
+        fid = self.face_ids.cpu().numpy().astype(np.int64)
+        flat = faces.reshape(-1).astype(np.int64)
+        first = np.zeros(len(flat), bool)
+        first[np.unique(flat, return_index=True)[1]] = True
+        new_index = np.where(first, flat, len(v) + np.cumsum(~first) - 1)
+        rgb = face_bgr_from_ids(fid)[:, ::-1]
+        out = np.zeros(len(v) + int((~first).sum()), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"),
+                                                            ("green", "u1"), ("blue", "u1")])
+        for a, name in enumerate("xyz"):
+            out[name][:len(v)] = v[:, a]
+            out[name][new_index] = v[flat, a]
+        for a, name in enumerate(("red", "green", "blue")):
+            out[name][new_index] = np.repeat(rgb[:, a], 3)
+        fo = np.zeros(len(faces), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+        fo["n"] = 3
+        fo["v"] = new_index.reshape(-1, 3)
+        head = ("ply\nformat binary_little_endian 1.0\n"
+                f"element vertex {len(out)}\nproperty float x\nproperty float y\nproperty float z\n"
+                "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+                f"element face {len(fo)}\nproperty list uchar int vertex_indices\nend_header\n")
+        with open(path, "wb") as f:
+            f.write(head.encode("ascii"))
+            f.write(out.tobytes())
+            f.write(fo.tobytes())
+
+
+def encode_mesh(vertices, faces, bits=16, attempts=3, iterations=10, eps=1.0, seed=0, device="cuda"):
+    """Code a triangle mesh: ``bits`` levels (1..16) of the balanced 2-means split, ``attempts`` tries
+    of up to ``iterations`` Lloyd steps per group stopping at a centre shift of ``eps`` mesh units
+    (the reference's cv::kmeans(..., TermCriteria(10, 1.0), 3, ...)).  vertices [nv, 3] (stored as
+    f32, finite, 2^bits <= nv <= 2^21), faces int [nf, 3].  The seeds are sampled on the host from
+    ``numpy.random.default_rng(seed)``; the split runs on the current stream of ``device``.
+    Returns a ``MeshCode``."""
+    import torch
+    from . import _lib as L
+    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float32).reshape(-1, 3))
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] != 3 or not np.issubdtype(f.dtype, np.integer) or len(f) == 0:
+        raise ValueError("faces must be a non-empty integer array [nf, 3]")
+    bits, attempts, iterations = int(bits), int(attempts), int(iterations)
+    if not 1 <= bits <= 16:
+        raise ValueError("bits must be in 1..16")
+    if len(v) < 1 << bits:
+        raise ValueError(f"{len(v)} vertices cannot fill 2^{bits} classes")
+    if attempts < 1 or iterations < 1:
+        raise ValueError("attempts and iterations must be >= 1")
+    if not np.isfinite(v).all():
+        raise ValueError("non-finite vertex")
+    if f.min() < 0 or f.max() >= len(v):
+        raise ValueError("face index outside the vertex array")
+    f = np.ascontiguousarray(f.astype(np.int32))
+    k = grid_log2(v)
+    eps2 = eps_to_grid(eps, k)
+    draws = np.random.default_rng(seed).integers(0, 1 << 32, size=(attempts, (1 << bits) - 1), dtype=np.uint32)
+    need = L.lib.zp_mesh_code_ws_bytes(len(v), len(f), bits)
+    if need < 0:
+        raise ValueError(f"mesh sizes out of range: {len(v)} vertices, {len(f)} faces, {bits} bits")
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        vd, fd = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
+        dd = torch.from_numpy(draws.view(np.int32)).to(dev)
+        vid = torch.empty(len(v), dtype=torch.int32, device=dev)
+        fid = torch.empty(len(f), dtype=torch.int32, device=dev)
+        lut = torch.empty((1 << bits, 3), dtype=torch.float64, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        L.call("zp_mesh_code", vd.data_ptr(), len(v), fd.data_ptr(), len(f), bits, attempts, iterations, k, eps2,
+               dd.data_ptr(), vid.data_ptr(), fid.data_ptr(), lut.data_ptr(), ws.data_ptr(), L.stream_ptr(dev))
+        # the inputs and the workspace were allocated on this stream: frees are ordered behind the call
+    return MeshCode(v, f, bits, vid, fid, lut, draws)
