@@ -482,6 +482,60 @@ long long zp_pose_error_ws_bytes(int B, int n, int mode);
 int zp_pose_error(int B, const float* pts, int n, const double* R_est, const double* t_est,
                   const double* R_gt, const double* t_gt, int mode, double* out, void* ws, void* stream);
 
+/* ---- BOP pose errors: MSSD, MSPD, VSD ----------------------------------------------------------
+ * The three errors behind BOP's average recalls (lib/pysixd/pose_error.py:22-179; defaults in
+ * lib/pysixd/scripts/eval_calc_errors.py:37-53), batched over B pose pairs of one model.
+ * tests/bop_ref.py restates the semantics below in numpy.
+ *
+ * zp_pose_error_sym: MSSD (pose_error.py:131-153) and MSPD (:156-179) over a set of S symmetry
+ * transformations (misc.py:206-254; zebrapose_amd.metric.symmetry_transformations builds it).
+ *   pts f32 [n][3]; R_* f64 [B][9] row-major, t_* f64 [B][3]; sym_R f64 [S][9] row-major, sym_t f64
+ *   [S][3]; K f64 [B][4] = (fx, fy, cx, cy), read by ZP_METRIC_MSPD only (else it may be NULL);
+ *   out f64 [B].  All arithmetic is f64, as in the reference.
+ *   Per symmetry s: R_s = R_gt sym_R[s], t_s = R_gt sym_t[s] + t_gt.
+ *   MSSD: e_s = max_i || (R_est p_i + t_est) - (R_s p_i + t_s) ||.
+ *   MSPD: the same over the projections u = fx X / Z + cx, v = fy Y / Z + cy (misc.py:511-525); there
+ *         is no special case for Z <= 0: the reference divides too.
+ *   out[b] = min_s e_s.  Squared distances are compared and one square root is taken at the end;
+ *   max and min are exact, so the result is bitwise reproducible and independent of how the points
+ *   are partitioned.  A NaN distance (possible only with non-finite input or Z = 0) is ignored.
+ * 1 <= S <= 4096, n >= 1, B >= 1; anything else, or a NULL pointer, is ZP_ERR_ARG before any device
+ * call.  ws: zp_pose_error_sym_ws_bytes bytes (-1: bad sizes or mode).
+ *
+ * zp_vsd: the pixel stage of VSD (pose_error.py:84-128) on depth images that are already rendered
+ * (zebrapose_amd.metric.vsd_errors renders them with zp_render: this rasteriser's depth, not OpenGL's).
+ *   depth_est, depth_gt f32 [B][H][W] and depth_test f32 [n_test][H][W], 0 = no surface; pose b reads
+ *   test image test_index[b] (i32 [B] on the device; an index outside [0, n_test) is read as the
+ *   nearest valid one), or image b when test_index is NULL (then n_test >= B).  K f64 [B][4] as
+ *   above.  taus is a HOST array of ntau tolerances (copied at the call); diameter f64 [B] on the
+ *   device, or NULL for distances that are not normalised.  out f64 [B][ntau]; counts i32
+ *   [B][2 + ntau] = (union, inter, cost_0 ..), or NULL.
+ *   Distance image (misc.py:565-588), per pixel (x, y) and image d, every step one IEEE f64
+ *   operation: pX = (x - cx) / fx, pY = (y - cy) / fy, z = f64(d),
+ *   dist = sqrt(((pX z)^2 + (pY z)^2) + z^2).
+ *   Visibility, visib_mode 'bop19' (visibility.py:34-36, 72-73):
+ *     visib(m) = (f32(dist_m) - f32(dist_test) <= f32(delta) || dist_test == 0) && dist_m > 0
+ *     visib_gt = visib(gt); visib_est = visib(est) || (visib_gt && dist_est > 0).
+ *   union / inter = pixel counts of visib_gt | visib_est and visib_gt & visib_est; on the inter
+ *   pixels dists = |dist_gt - dist_est|, divided by diameter[b] when given; cost_k = #(dists >=
+ *   taus[k]), the 'step' cost (pose_error.py:117-118).
+ *   out[b][k] = f64(cost_k + (union - inter)) / f64(union), or 1.0 when union == 0.
+ *   Every counter is an integer, so the result is exact and independent of the order of the pixels.
+ * Left out: the 'tlinear' cost (pose_error.py:119-121) and visib_mode 'bop18' (visibility.py:29-32).
+ * 1 <= ntau <= 32, 1 <= B <= 65535, H, W >= 1, H * W < 2^31 - 1024, n_test >= 1; anything else, or a
+ * NULL pointer other than test_index, diameter and counts, is ZP_ERR_ARG before any device call.
+ * ws: zp_vsd_ws_bytes bytes (-1: bad sizes). */
+#define ZP_METRIC_MSSD 2
+#define ZP_METRIC_MSPD 3
+long long zp_pose_error_sym_ws_bytes(int B, int n, int S, int mode);
+int zp_pose_error_sym(int B, const float* pts, int n, const double* R_est, const double* t_est,
+                      const double* R_gt, const double* t_gt, const double* K, const double* sym_R,
+                      const double* sym_t, int S, int mode, double* out, void* ws, void* stream);
+long long zp_vsd_ws_bytes(int B, int H, int W, int ntau);
+int zp_vsd(int B, const float* depth_est, const float* depth_gt, const float* depth_test, int n_test,
+           const int* test_index, int H, int W, const double* K, double delta, const double* taus, int ntau,
+           const double* diameter, double* out, int* counts, void* ws, void* stream);
+
 /* ---- device crop pipeline --------------------------------------------
  * Replaces the DataLoader worker's crop_square_resize (bop_dataset_pytorch.py:36-72) of the image
  * (cv2.INTER_LINEAR -> S px) + transform_pre (:333-347: ToTensor + ImageNet Normalize on the BGR
