@@ -41,6 +41,11 @@
  *   zp_mesh_code       the offline coder Binary_Code_GT_Generator/Generate_Mesh_with_GT_Color
  *                      (Generate_Mesh_with_GT_Color.cpp:61-218 balanced 2-means split, :322-455 vertex /
  *                      face ids and the class -> 3D-point LUT), binary splits only
+ *   zp_mask_contour    the visible contour handed to the refinement (test.py:300-307: cv2.findContours
+ *                      of the entire mask, the visible-mask filter, mapping_pixel_position_to_original_position)
+ *   zp_edge_refine_step  one iteration of py_edge_refine (edge_refine/examples/edge_refine.cpp:68-173:
+ *                      cv::findContours of the rendered silhouette, the nearest-contour match, the
+ *                      6 x 6 normal equations and the pose update), on zp_render's depth
  */
 #ifndef ZP_H_
 #define ZP_H_
@@ -669,6 +674,75 @@ long long zp_mesh_code_ws_bytes(int nv, int nf, int bits);
 int zp_mesh_code(const float* verts, int nv, const int* faces, int nf, int bits, int attempts, int iterations,
                  int grid_log2, long long eps2_q, const uint32_t* draws, int* vertex_ids, int* face_ids, double* lut,
                  void* ws, void* stream);
+
+/* ---- edge refinement -----------------------------------------------------------------------
+ * The refine = True branch of the reference's inference (test.py:276-313): the visible contour of the
+ * object's mask (zp_mask_contour) and py_edge_refine's Gauss-Newton iteration against it
+ * (zp_edge_refine_step, edge_refine/examples/edge_refine.cpp:68-173), batched over B crops / poses.
+ * The reference needs OpenGL, Eigen and OpenCV for it; the semantics are restated here and, in numpy,
+ * in tests/refine_ref.py.  R f64 [B][9] row-major, t f64 [B][3], K f64 [B][4] = (fx, fy, cx, cy), as
+ * zp_render and zp_pnp_ransac; all arithmetic on reals is f64 (the reference: f32 Eigen).
+ *
+ * Outer border of a binary image (both functions): pad the image with one ring of unset pixels; the
+ * OUTSIDE is the 4-connected component of unset pixels containing the ring; a set pixel is an
+ * outer-border pixel iff one of its four neighbours is in the outside.  This is the pixel set of
+ * cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_NONE) over all 8-connected components; borders of
+ * holes, and components lying inside a hole, are not part of it.  Order: row-major (y, then x).
+ * A pixel the tracer visits twice appears once.
+ * The outside is found by row and column sweeps repeated until nothing changes, at most 4 (H + W)
+ * times; an image that needs more (no rendered silhouette does) is reported, never waited for.
+ * Images: 1 <= H, W <= 32768 and H * 32 ceil(W / 32) <= 2^19 (640 x 480 and 720 x 540 fit), 1 <= B <=
+ * 65535; anything else, or a NULL pointer that is not optional, is ZP_ERR_ARG before any device call.
+ *
+ * zp_mask_contour (test.py:300-307): entire u8 [B][S][S] (non-zero = set), visible u8 [B][S][S] or
+ * NULL, bbox i32 [B][4] = (x, y, w, h) -> counts i32 [B], xy i32 [B][cap][2].
+ *   An outer-border pixel (x, y) of `entire` is kept iff x > 0, y > 0 and any of visible[y-1 .. y]
+ *   [x-1 .. x] is non-zero (visible NULL: iff x > 0 and y > 0).  It is written as
+ *   X = trunc(f64(w) / S * x + bx), Y = trunc(f64(h) / S * y + by)
+ *   (mapping_pixel_position_to_original_position: f64 divide, multiply, add, truncation toward zero);
+ *   duplicates after truncation are kept.  counts[b] is the true count, entries past cap are dropped;
+ *   counts[b] = -1 when the sweep cap was hit.
+ *
+ * zp_edge_refine_step: one iteration for B poses, on the depth images f32 [B][H][W] (0 = background)
+ * that zp_render produced at those poses with K' = (fx, fy, cx + 1/2, cy + 1/2): the reference's
+ * renderer has its pixel centres at integers (renderer.cpp:115-118), zp_render samples at
+ * half-integers.  The step itself takes the unshifted K.
+ *   counts i32 [B], xy i32 [B][cap][2]: the observed contour, as zp_mask_contour writes it; pose b
+ *   uses its first min(counts[b], cap) points, each coordinate saturated to +-2^20.  1 <= cap <= 2^20.
+ *   silhouette: depth > 0; border list: its outer border.
+ *   match:    per observed point (x, y) the border pixel (xc, yc) with the smallest integer squared
+ *             distance, ties to the lowest row-major index.
+ *   residual: e = (x - xc, y - yc);  cost[b] = sum |e|^2, an exact integer.
+ *   geometry: d = f64(depth[yc][xc]); Xc = (d (xc - cx) / fx, d (yc - cy) / fy, d); Xb = R^T (Xc - t);
+ *             Jc = [[-fx / d, 0, fx Xc.x / d^2], [0, -fy / d, fy Xc.y / d^2]]; Jt = Jc R;
+ *             Jr = -Jt [Xb]x; J = [Jr | Jt] (2 x 6);  H = sum J^T J;  b = -sum J^T e.
+ *             The sums run over a fixed partition and a fixed tree, without floating-point atomics:
+ *             two runs give the same bits.
+ *   solve:    (diag(lambda_rot x 3, lambda_trans x 3) + H) theta = b (Cholesky); both lambdas > 0.
+ *   update:   E = exp([theta_r]x) by Rodrigues (the series below |theta_r| = 1e-8);
+ *             R_out = R E; t_out = t + R_out theta_t (Eigen's rotate, then translate, :163-166).
+ *   status i32 [B]: 0 stepped; 1 fewer than 20 border pixels, or no observed point (:96-100);
+ *             2 the sweep cap was hit.  With 1 and 2 the pose is copied through bit for bit, cost is 0.
+ *   units:    those of depth and t.  The reference works in metres with lambda_rot = 5000,
+ *             lambda_trans = 500000; for millimetres pass lambda_trans * 0.001^2 = 0.5 and the same
+ *             lambda_rot: the problem is then the same one.
+ *   Optional outputs (NULL: not written): border_n i32 [B]; border_xy i32 [B][bcap][2] (the first bcap
+ *   border pixels); match i32 [B][cap] (index into the border list, -1 past the points used); Hb f64
+ *   [B][27]: the upper triangle of H by rows (21 values), then b.
+ *   R_out / t_out must not be R / t.  ws: zp_edge_refine_ws_bytes bytes (-1: bad sizes); it holds the
+ *   border pixels past the 4096 kept on chip.
+ * Deviations from the reference: f64 for f32; the exact f32 depth for SRT3D's 16-bit depth buffer, and
+ * no 0.001 - 50 m clip; contours as sets (row-major, no repeats) for traces; the tie rule (the reference
+ * takes the first in trace order); the border of all components, where the reference drops contours
+ * shorter than 20 and matches against contours[0] alone; e from the pixel itself, where the
+ * reference re-projects the back-projected point (the same up to rounding). */
+int zp_mask_contour(int B, int S, const uint8_t* entire, const uint8_t* visible, const int* bbox, int cap,
+                    int* counts, int* xy, void* stream);
+long long zp_edge_refine_ws_bytes(int B, int H, int W);
+int zp_edge_refine_step(int B, int H, int W, const float* depth, const int* counts, const int* xy, int cap,
+                        const double* R, const double* t, const double* K, double lambda_rot, double lambda_trans,
+                        double* R_out, double* t_out, long long* cost, int* status, int* border_n, int* border_xy,
+                        int bcap, int* match, double* Hb, void* ws, void* stream);
 
 /* ---- optimizer ----------------------------------------------------------------------- */
 /* torch.optim.Adam (no weight decay, amsgrad off) over one flat f32 buffer; step >= 1 */
