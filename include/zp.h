@@ -744,6 +744,67 @@ int zp_edge_refine_step(int B, int H, int W, const float* depth, const int* coun
                         double* R_out, double* t_out, long long* cost, int* status, int* border_n, int* border_xy,
                         int bcap, int* match, double* Hb, void* ws, void* stream);
 
+/* ---- ICP refinement -------------------------------------------------------------------------
+ * The reference's depth-based refiner (zebrapose/icp/icp_utils.py:7-176): render the model's depth at
+ * the estimated pose, back-project it and the measured depth to point clouds (zp_depth_points, called
+ * once for each), and run point-to-point ICP from the rendered cloud to the measured one (zp_icp),
+ * batched over B poses.  The reference needs OpenGL and sklearn for it and takes one pose at a time;
+ * the semantics are restated here and, in numpy, in tests/icp_ref.py.  All reals are f64; R f64 [B][9]
+ * row-major, t f64 [B][3], K f64 [B][4] = (fx, fy, cx, cy).  Neither function synchronises the host or
+ * uses atomics; two runs give the same bits.  Bad sizes or values, or a NULL pointer that is not
+ * optional, are ZP_ERR_ARG before any device call.  The *_ws_bytes functions return -1 for sizes out
+ * of range and otherwise the workspace the call needs, which is 0 for both today (ws may then be NULL):
+ * everything lives in registers and LDS.
+ *
+ * zp_depth_points (rgbd_to_point_cloud, :7-13): depth f32 [B][H][W] -> counts i32 [B], pts f64 [B][cap][3].
+ *   A pixel (u, v) counts iff its depth is finite and > 0 (the reference's nonzero() would also take
+ *   negative values and NaN).  Its point is z = f64(depth), x = ((u - cx) * z) / fx,
+ *   y = ((v - cy) * z) / fy, each step one f64 operation, u and v the integer pixel indices.
+ *   filter (optional) f64 [B][4] = (centre x, y, z, radius), device memory, with the host scalar factor
+ *   >= 0 (:147-148): with lim = factor * radius a point is kept iff (dx dx + dy dy) + dz dz < lim * lim,
+ *   d = point - centre.  Kept points are written in row-major pixel order; counts[b] is the true count,
+ *   entries past cap are dropped.
+ *   stats (optional) f64 [B][4]: the centroid of ALL kept points (sum / count) and the largest distance
+ *   sqrt((dx dx + dy dy) + dz dz) of one from it (:139-141); zeros when nothing is kept.  It has the
+ *   filter's layout: the call for the measured depth reads the stats of the call for the rendered one.
+ *   1 <= B <= 65535, 1 <= H, W <= 16384, H W <= 2^24, 1 <= cap <= 2^24, B cap <= 2^28; stats != filter.
+ *
+ * zp_icp (ICPRefiner.refine from :149 on, icp :83-126, best_fit_transform :35-80): source = the rendered
+ * cloud (src_pts f64 [B][src_cap][3], src_counts i32 [B]), destination = the measured one, both as
+ * zp_depth_points writes them; counts are clamped to [0, cap].  One workgroup per pose, one launch.
+ *   status 1: n_src = 0.  status 2: n_dst < n_src * min_fraction (the reference: 1/20), or n_dst = 0.
+ *   subsample: n = min(n_src, n_dst, N); entry i < n of each side is point floor(draw[i] * count) of its
+ *             list, draws_src / draws_dst f64 [B][N] uniform in [0, 1) (sampling with replacement, as
+ *             np.random.choice, from the caller's generator, not numpy's stream).  1 <= N <= 4096.
+ *   iterate:  at most max_iterations (>= 1) times: per source point the destination point with the
+ *             smallest (dx dx + dy dy) + dz dz, ties to the lowest index; the best-fit transform from
+ *             the source points to their neighbours; the source points moved by it; stop after the move
+ *             when |prev_error - mean distance| < tolerance (distances Euclidean, prev_error starts at
+ *             0 and follows the mean).
+ *   fit:      centroids cA, cB; mode 1 (depth_only): R = I, t = cB - cA.  Otherwise H = sum (a - cA)
+ *             (b - cB)^T = U S V^T, R = V U^T with the last singular pair's sign chosen so that det R = 1,
+ *             t = cB - R cA, and in mode 2 (no_depth) t_z = 0.  The solver is a 3 x 3 Jacobi iteration on
+ *             H^T H (the reference: LAPACK's SVD).
+ *   result:   T = the fit from the original subsample to the final source points (:119); in mode 2 a T
+ *             whose rotation angle atan2(|sin|, cos) exceeds angle_limit (the reference: 20 degrees in
+ *             radians) is dropped, status 3.  R_out = T_R R, t_out = T_R t + T_t.
+ *   With status 1, 2 and 3 the pose is copied through bit for bit; iterations is 0 and mean_error 0 for
+ *   1 and 2.  iterations i32 [B]: iterations run (the reference's i + 1); mean_error f64 [B]: the mean
+ *   distance of the last one.
+ *   Optional outputs (NULL: not written): nn i32 [B][N], the neighbour of each source point in the last
+ *   iteration run as an index into the destination subsample, -1 from n on; T f64 [B][16] row-major,
+ *   the fitted transform (also with status 3; the identity with 1 and 2).
+ *   R_out / t_out must not be R / t.  tolerance must not be NaN, max_iterations <= 100000. */
+long long zp_depth_points_ws_bytes(int B, int H, int W, int cap);
+int zp_depth_points(int B, int H, int W, const float* depth, const double* K, int cap, const double* filter,
+                    double factor, int* counts, double* pts, double* stats, void* ws, void* stream);
+long long zp_icp_ws_bytes(int B, int N);
+int zp_icp(int B, int N, const double* src_pts, const int* src_counts, int src_cap, const double* dst_pts,
+           const int* dst_counts, int dst_cap, const double* draws_src, const double* draws_dst, int max_iterations,
+           double tolerance, int mode, double min_fraction, double angle_limit, const double* R, const double* t,
+           double* R_out, double* t_out, int* status, int* iterations, double* mean_error, int* nn, double* T,
+           void* ws, void* stream);
+
 /* ---- optimizer ----------------------------------------------------------------------- */
 /* torch.optim.Adam (no weight decay, amsgrad off) over one flat f32 buffer; step >= 1 */
 int zp_adam(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n,

@@ -149,6 +149,11 @@ _SIGS = {
     "zp_edge_refine_ws_bytes": (i64, [i32, i32, i32]),
     "zp_edge_refine_step": (i32, [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, f64, f64, vp, vp, vp, vp, vp, vp, i32,
                                   vp, vp, vp, vp]),
+    "zp_depth_points_ws_bytes": (i64, [i32, i32, i32, i32]),
+    "zp_depth_points": (i32, [i32, i32, i32, vp, vp, i32, vp, f64, vp, vp, vp, vp, vp]),
+    "zp_icp_ws_bytes": (i64, [i32, i32]),
+    "zp_icp": (i32, [i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, f64, i32, f64, f64, vp, vp, vp, vp, vp, vp, vp,
+                     vp, vp, vp, vp]),
 }
 
 
