@@ -90,6 +90,10 @@ def epnp(pw, uv, K):
     rho = np.array([np.sum((cws[a] - cws[b]) ** 2) for a, b in pairs])
 
     def lsq(A, b):
+        # a degenerate set (e.g. one 3D point repeated) drives the betas to 0 / 0: the C++ code
+        # carries the NaN through to a rejected model, LAPACK would raise on it
+        if not (np.all(np.isfinite(A)) and np.all(np.isfinite(b))):
+            return np.full(A.shape[1], np.nan)
         return np.linalg.lstsq(A, b, rcond=None)[0]
 
     def gauss_newton(betas):
@@ -136,6 +140,10 @@ def epnp(pw, uv, K):
             ccs, pcs = -ccs, -pcs
         pc0, pw0 = pcs.mean(0), pw.mean(0)
         abt = (pcs - pc0).T @ (pw - pw0)
+        if not np.all(np.isfinite(abt)):  # no pose from this candidate (see lsq)
+            if best is None:
+                best = (np.nan, np.full((3, 3), np.nan), np.full(3, np.nan))
+            continue
         U, _, Vt = np.linalg.svd(abt)
         R = U @ Vt
         if np.linalg.det(R) < 0:
@@ -162,9 +170,10 @@ def ransac_err(R, t, pw_f32, uv_f32, K):
     return du * du + dv * dv
 
 
-def solve_pnp_ransac(pw, uv, K, iterations=150, reprojection_error=2.0, confidence=0.99):
-    """-> dict(success, R, t, best, inliers, good[iterations]) for one crop."""
-    pw = np.asarray(pw, dtype=np.float32)
+def solve_pnp_ransac(pw, uv, K, iterations=150, reprojection_error=2.0, confidence=0.99, pw_dtype=np.float32):
+    """-> dict(success, R, t, best, inliers, good[iterations]) for one crop.  pw_dtype=np.float64
+    keeps the model points unrounded (for perturbation studies below f32 resolution)."""
+    pw = np.asarray(pw, dtype=pw_dtype)
     uv = np.asarray(uv, dtype=np.float32)
     n = len(pw)
     mp = 5

@@ -56,3 +56,28 @@ def test_epnp_refinement_matches_oracle(host_check, tmp_path, n, noise):
     Rr, tr = pnp_ref.epnp(pw, uv, K)
     np.testing.assert_allclose(out[:9].reshape(3, 3), Rr, atol=1e-9)
     np.testing.assert_allclose(out[9:], tr, rtol=1e-9, atol=1e-9 * np.abs(tr).max())
+
+
+def test_collinear_points_still_give_a_rotation(host_check, tmp_path):
+    """Procrustes on a rank-1 ABt (exactly collinear model points): the hypotheses and the
+    refinement return a proper rotation, as an SVD-based U V^T does, not a sheared matrix."""
+    from tests import pnp_cases
+    pw, uv, _, _ = pnp_cases.degenerate_cases()["collinear"]
+    n = len(pw)
+    sub = pnp_ref.cv_rng_subsets(n, 20, 5).astype(np.int32)
+    fin, fout = tmp_path / "in.bin", tmp_path / "out.bin"
+    with open(fin, "wb") as f:
+        f.write(struct.pack("ii", n, len(sub)))
+        f.write(np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]]).tobytes())
+        f.write(pw.tobytes())
+        f.write(uv.astype(np.float32).tobytes())
+        f.write(sub.tobytes())
+        f.write(struct.pack("i", n))
+        f.write(np.arange(n, dtype=np.int32).tobytes())
+    subprocess.run([host_check, str(fin), str(fout)], check=True, capture_output=True)
+    out = np.fromfile(fout, dtype=np.float64).reshape(-1, 12)
+    assert len(out) == 21
+    for m in out:
+        assert np.all(np.isfinite(m))
+        Rm = m[:9].reshape(3, 3)
+        assert np.abs(Rm.T @ Rm - np.eye(3)).sum(1).max() <= 1e-9 and abs(np.linalg.det(Rm) - 1) <= 1e-9

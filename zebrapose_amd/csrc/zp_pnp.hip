@@ -159,6 +159,24 @@ ZP_HD void procrustes(const double* abt, double* Rm) {
     double u[3];
     for (int i = 0; i < 3; ++i) u[i] = abt[i * 3 + 0] * V[k * 3 + 0] + abt[i * 3 + 1] * V[k * 3 + 1] + abt[i * 3 + 2] * V[k * 3 + 2];
     double n = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    if (k == 0 && n == 0) {  // ABt = 0: any orthonormal U (an SVD returns one)
+      u[0] = n = 1.0;
+      u[1] = u[2] = 0.0;
+    }
+    if (k == 1 && n <= 1e-6 * (sqrt(fabs(ev[0])) + 1e-300)) {
+      // rank 1 (collinear points): ABt v1 is rounding noise, not orthogonal to u0; take the unit
+      // vector orthogonal to u0 nearest the axis u0 is least aligned with, so that R is a rotation.
+      // 1e-6 where the rank-2 test below has 1e-12: V comes from the eigenvectors of ABt^T ABt,
+      // so ABt v1 carries about 1e-8 s0 of u0, and a u1 below 1e-6 s0 would be off the orthogonal
+      // by more than 1e-2.  The rank-2 test serves the exactly planar model (a zero column of
+      // ABt) and keeps its bound.  Sets with s1 > 1e-6 s0 keep their bits.
+      const double a[3] = {U[0], U[3], U[6]};
+      int m = 0;
+      for (int j = 1; j < 3; ++j)
+        if (fabs(a[j]) < fabs(a[m])) m = j;
+      for (int i = 0; i < 3; ++i) u[i] = (i == m ? 1.0 : 0.0) - a[m] * a[i];
+      n = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    }
     if (k == 2 && n <= 1e-12 * (sqrt(fabs(ev[0])) + 1e-300)) {  // rank 2: u2 = u0 x u1
       const double ax = U[0], ay = U[3], az = U[6], bx = U[1], by = U[4], bz = U[7];
       u[0] = ay * bz - az * by;
@@ -520,7 +538,8 @@ ZP_HD bool epnp_small(int m, const double (*pw)[3], const double* uu, const doub
 
 // Parallel cyclic Jacobi on the symmetric 12x12 A (LDS), eigenvectors accumulated in V (LDS,
 // columns): threads 0..63 of the block work (6 disjoint rotations per round, circle-method
-// pairing, 11 rounds per sweep), every thread of the block takes part in the barriers.
+// pairing, 11 rounds per sweep), every thread of the block takes part in the barriers and leaves
+// the sweep loop at the same sweep.
 __device__ void par_jacobi12(double* A, double* V, double (*cs)[2], int* rotated) {
   const int lane = threadIdx.x;
   const bool worker = lane < 64;
@@ -571,7 +590,12 @@ __device__ void par_jacobi12(double* A, double* V, double (*cs)[2], int* rotated
         }
       __syncthreads();
     }
-    if (!*rotated) break;
+    // every thread reads the flag, then the block meets before lane 0 resets it for the next
+    // sweep: without this barrier a wave of a multi-wave block (k_pnp_refine) could see the reset
+    // instead of the sweep's value and leave the loop alone
+    const int rot = *rotated;
+    __syncthreads();
+    if (!rot) break;
   }
 }
 
