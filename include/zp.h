@@ -775,7 +775,9 @@ int zp_edge_refine_step(int B, int H, int W, const float* depth, const int* coun
  *   status 1: n_src = 0.  status 2: n_dst < n_src * min_fraction (the reference: 1/20), or n_dst = 0.
  *   subsample: n = min(n_src, n_dst, N); entry i < n of each side is point floor(draw[i] * count) of its
  *             list, draws_src / draws_dst f64 [B][N] uniform in [0, 1) (sampling with replacement, as
- *             np.random.choice, from the caller's generator, not numpy's stream).  1 <= N <= 4096.
+ *             np.random.choice, from the caller's generator, not numpy's stream).  1 <= N <= 4096.  A draw
+ *             outside [0, 1) still gives an index: count - 1 from draw * count >= count on, 0 for a
+ *             negative product and for NaN.
  *   iterate:  at most max_iterations (>= 1) times: per source point the destination point with the
  *             smallest (dx dx + dy dy) + dz dz, ties to the lowest index; the best-fit transform from
  *             the source points to their neighbours; the source points moved by it; stop after the move
@@ -784,7 +786,9 @@ int zp_edge_refine_step(int B, int H, int W, const float* depth, const int* coun
  *   fit:      centroids cA, cB; mode 1 (depth_only): R = I, t = cB - cA.  Otherwise H = sum (a - cA)
  *             (b - cB)^T = U S V^T, R = V U^T with the last singular pair's sign chosen so that det R = 1,
  *             t = cB - R cA, and in mode 2 (no_depth) t_z = 0.  The solver is a 3 x 3 Jacobi iteration on
- *             H^T H (the reference: LAPACK's SVD).
+ *             H^T H, its v2 and v3 polished against H itself where s2 <= 1e-3 s1 (the reference: LAPACK's
+ *             SVD).  Where the rotation is not unique (H of rank 0 or 1) it is the identity, or one of the
+ *             best rotations.
  *   result:   T = the fit from the original subsample to the final source points (:119); in mode 2 a T
  *             whose rotation angle atan2(|sin|, cos) exceeds angle_limit (the reference: 20 degrees in
  *             radians) is dropped, status 3.  R_out = T_R R, t_out = T_R t + T_t.

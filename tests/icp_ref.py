@@ -128,8 +128,14 @@ def rotation_angle(T):
 
 
 def draw_indices(draws, count):
-    """floor(draw * count): sampling with replacement from uniform draws in [0, 1)."""
-    return np.minimum((np.asarray(draws, np.float64) * float(count)).astype(np.int64), count - 1)
+    """floor(draw * count): sampling with replacement from uniform draws in [0, 1).  A draw outside
+    that range still gives an index, as on the device: count - 1 from draw * count >= count on (1.0
+    and above, +inf), 0 for a negative product, -0.0 and NaN."""
+    v = np.asarray(draws, np.float64) * float(count)
+    with np.errstate(invalid="ignore"):
+        inside = (v >= 0.0) & (v < float(count))
+        idx = np.where(inside, v, 0.0).astype(np.int64)
+        return np.where(v >= float(count), count - 1, idx)
 
 
 def icp_pose(src_pts, dst_pts, draws_src, draws_dst, R, t, N=None, max_iterations=200, tolerance=5e-7, mode=FULL,

@@ -63,6 +63,14 @@ def fill_passes(img):
         o, passes = n, passes + 1
 
 
+def capped(img):
+    """Whether the device gives up on this image: the fill's last changing pass is pass 4 (H + W) or
+    later, so none of its 4 (H + W) passes sees that nothing changes (zp_mask_contour: counts = -1;
+    zp_edge_refine_step: status 2)."""
+    H, W = np.asarray(img).shape
+    return fill_passes(img) >= 4 * (H + W)
+
+
 def mask_contour(entire, visible, bbox):
     """test.py:300-307 for one crop: entire [S, S], visible [S, S] or None, bbox (x, y, w, h) ->
     int32 [n, 2] image pixels (all of them: the device's counts is n, its list the first cap)."""
@@ -119,7 +127,7 @@ def step(depth, pts, R, t, K, lambda_rot, lambda_trans):
     H_, W_ = depth.shape
     sil = depth > 0
     out = {"R": R.copy(), "t": t.copy(), "cost": 0, "Hb": np.zeros(27), "match": np.zeros(0, np.int64)}
-    if fill_passes(sil) >= 4 * (H_ + W_):
+    if capped(sil):
         out.update(status=2, border=np.zeros((0, 2), np.int64))
         return out
     border = border_list(sil)

@@ -105,6 +105,76 @@ def spiral(H, W):
     return a
 
 
+def staircase_cells(S):
+    """The cells (x, y) of a one-pixel corridor through a solid S x S image, in the order the outside
+    reaches them: staircases (right 1, down 1, ...) three columns apart, so that neighbouring ones
+    touch only at corners, joined alternately at their far and near ends into one serpentine with
+    its mouth at (0, 1) on the frame.  Row and column sweeps both stop at every corner: a fill pass
+    (rows, then columns) advances one stair."""
+    free = np.zeros((S, S), bool)
+    k = 0
+    while 3 * k + 4 <= S - 2:
+        y_end = S - 3 - 3 * k
+        for y in range(1, y_end + 1):
+            free[y, y + 3 * k:y + 3 * k + 2] = True
+        if 3 * (k + 1) + 4 <= S - 2:
+            if k % 2 == 0:
+                free[y_end - 3:y_end + 1, S - 2] = True  # the far ends, down the last inner column
+            else:
+                free[1, 3 * k + 3] = True                # the near ends, along the first inner row
+        k += 1
+    free[1, 0] = True
+    # breadth-first from the mouth: the order of arrival
+    order, seen, front = [], np.zeros_like(free), [(0, 1)]
+    seen[1, 0] = True
+    while front:
+        order += front
+        nxt = []
+        for x, y in front:
+            for u, v in ((x + 1, y), (x - 1, y), (x, y + 1), (x, y - 1)):
+                if 0 <= u < S and 0 <= v < S and free[v, u] and not seen[v, u]:
+                    seen[v, u] = True
+                    nxt.append((u, v))
+        front = nxt
+    assert len(order) == free.sum()  # one corridor: everything is reached
+    return order
+
+
+def staircase(S, length=None):
+    """u8 [S, S]: solid but for the first `length` cells (default: all) of staircase_cells(S)."""
+    a = np.ones((S, S), np.uint8)
+    cells = staircase_cells(S)
+    for x, y in cells[:len(cells) if length is None else length]:
+        a[y, x] = 0
+    return a
+
+
+STAIR_S = 54  # the smallest S at which the whole serpentine takes more than 4 (S + S) passes
+
+
+_STAIRS = {}
+
+
+def staircase_at_cap(S=None):
+    """(over, last, under): the whole serpentine (more changing passes than the cap 4 (S + S)), the
+    longest prefix whose last changing pass is pass `cap` (the fill is complete, the device's next
+    pass would have found nothing to do, and there is no next pass), and the longest whose last
+    changing pass is pass `cap - 1` (the device's last pass sees that nothing changes)."""
+    S = S or STAIR_S
+    if S not in _STAIRS:
+        cap, n = 8 * S, len(staircase_cells(S))
+
+        def longest(passes):  # the pass count does not fall as the corridor grows
+            lo, hi = 1, n
+            while lo < hi:
+                mid = (lo + hi + 1) // 2
+                lo, hi = (mid, hi) if RF.fill_passes(staircase(S, mid)) <= passes else (lo, mid - 1)
+            return staircase(S, lo)
+
+        _STAIRS[S] = (staircase(S), longest(cap), longest(cap - 1))
+    return _STAIRS[S]
+
+
 @pytest.mark.parametrize("name", sorted(GRIDS))
 def test_border_sets_on_hand_written_grids(name):
     img, want = grid(name)
@@ -232,3 +302,43 @@ def test_short_border_and_no_points_copy_the_pose_through():
     depth[2:12, 2:12] = 500.0
     assert RF.step(depth, np.zeros((0, 2)), R, t, [100, 100, 8, 8], 5000.0, 0.5)["status"] == 1
     assert RF.step(depth, [[5, 5]], R, t, [100, 100, 8, 8], 5000.0, 0.5)["status"] == 0
+
+
+def border_of(n):
+    """A 16 x 16 depth image whose silhouette has exactly n = 19 or 20 border pixels: a 6 x 6 square
+    (20: its perimeter), less one corner (19: the corner's diagonal neighbour has no unset 4-neighbour)."""
+    d = np.zeros((16, 16), np.float32)
+    d[5:11, 4:10] = 500.0
+    if n == 19:
+        d[5, 4] = 0.0
+    return d
+
+
+def test_min_border_boundary():
+    R, t = RF.rodrigues([1, 2, 3], 0.4), np.array([1.0, 2.0, 500.0])
+    for n, status in [(19, 1), (20, 0)]:
+        d = border_of(n)
+        assert len(RF.border_list(d > 0)) == n
+        assert RF.step(d, [[5, 5], [12, 3]], R, t, [100, 100, 8, 8], 5000.0, 0.5)["status"] == status
+
+
+def test_staircase_serpentine_reaches_the_sweep_cap():
+    """STAIR_S is the smallest size whose serpentine outlasts the cap; of the two tuned prefixes one
+    stops changing in pass cap - 1 (the fill succeeds) and one in pass cap (complete, but reported as
+    capped: the device has no pass left in which to see that nothing changes)."""
+    S, cap = STAIR_S, 8 * STAIR_S
+    assert RF.fill_passes(staircase(S - 1)) <= 8 * (S - 1) and RF.fill_passes(staircase(S)) > cap
+    over, last, under = staircase_at_cap()
+    assert RF.fill_passes(over) > cap and RF.fill_passes(last) == cap and RF.fill_passes(under) == cap - 1
+    assert (last != under).sum() >= 1 and (over != last).sum() >= 1
+    R, t = RF.rodrigues([1, 2, 3], 0.4), np.array([1.0, 2.0, 500.0])
+    K = [100, 100, S / 2, S / 2]
+    for m, status in [(over, 2), (last, 2), (under, 0)]:
+        s = RF.step(np.where(m != 0, 500.0, 0.0).astype(np.float32), [[5, 5], [30, 40]], R, t, K, 5000.0, 0.5)
+        assert s["status"] == status
+        if status == 2:
+            assert np.array_equal(s["R"], R) and np.array_equal(s["t"], t) and s["cost"] == 0 and len(s["border"]) == 0
+    # in the prefix that succeeds the whole corridor is outside: every wall pixel beside it is border
+    b = RF.outer_border(under)
+    cells = np.array(staircase_cells(S)[:int((under == 0).sum())])
+    assert b[cells[:, 1] + 1, cells[:, 0]].sum() + b[cells[:, 1] - 1, cells[:, 0]].sum() > len(cells) / 2

@@ -68,9 +68,47 @@ __device__ __forceinline__ void cross3(const double* a, const double* b, double*
 }
 __device__ __forceinline__ double norm3(const double* a) { return sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]); }
 
+// V (columns: eigenvectors of H^T H, largest first) of a thin cloud, polished against H itself.  H^T H
+// holds s2^2 beside s1^2, so its eigenvectors fix v2 against v3 only to 2^-53 s1^2 / (s2^2 - s3^2); v1 is
+// good to 2^-53.  H v2 and H v3 hold s2 and s3 themselves: v2 and v3 are turned in their plane until
+// those two are orthogonal (one-sided Jacobi on one pair; from a V that close the second turn is already
+// rounding), which makes them as accurate as a 2^-53 |H| change of H allows.
+__device__ void polish_v(const double* Hm, double (&V)[3][3]) {
+  for (int turn = 0; turn < 3; ++turn) {
+    double g[3], h[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      g[i] = (Hm[3 * i] * V[0][1] + Hm[3 * i + 1] * V[1][1]) + Hm[3 * i + 2] * V[2][1];
+      h[i] = (Hm[3 * i] * V[0][2] + Hm[3 * i + 1] * V[1][2]) + Hm[3 * i + 2] * V[2][2];
+    }
+    double a = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
+    double b = (h[0] * h[0] + h[1] * h[1]) + h[2] * h[2];
+    const double c = (g[0] * h[0] + g[1] * h[1]) + g[2] * h[2];
+    if (b > a) {  // v2 is the longer of the two; a turn (below 45 degrees) keeps it the longer
+      const double a_ = a;
+      a = b, b = a_;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double v_ = V[k][1];
+        V[k][1] = V[k][2], V[k][2] = v_;
+      }
+    }
+    if (fabs(c) <= 1e-15 * sqrt(a * b) || c == 0.0) break;
+    const double theta = (b - a) / (2.0 * c);
+    const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double vp = V[k][1], vq = V[k][2];
+      V[k][1] = cs * vp - sn * vq, V[k][2] = sn * vp + cs * vq;
+    }
+  }
+}
+
 // Kabsch rotation of H = sum a b^T = U S V^T: R = V U^T with the reflection fix, as
 // R = v1 u1^T + v2 u2^T + (v1 x v2)(u1 x u2)^T.  v1, v2: the two leading eigenvectors of H^T H (cyclic
-// Jacobi, every index a constant so the matrices stay in registers), u_k = H v_k / |H v_k|.
+// Jacobi, every index a constant so the matrices stay in registers; polished against H where the cloud
+// is thin), u_k = H v_k / |H v_k|.
 __device__ void kabsch(const double* Hm, double* R) {
   double A[3][3], V[3][3];
 #pragma unroll
@@ -128,6 +166,8 @@ __device__ void kabsch(const double* Hm, double* R) {
   ZP_ICP_CSWAP(0, 2)
   ZP_ICP_CSWAP(1, 2)
 #undef ZP_ICP_CSWAP
+  // a thin cloud, s2 <= 1e-3 s1 (a thicker one keeps its bits; its V is good to 1e-10 or better)
+  if (ev[1] < 1e-6 * ev[0]) polish_v(Hm, V);
   const double v1[3] = {V[0][0], V[1][0], V[2][0]}, v2[3] = {V[0][1], V[1][1], V[2][1]};
   double u1[3], u2[3], v3[3], u3[3];
 #pragma unroll
