@@ -46,6 +46,11 @@
  *   zp_edge_refine_step  one iteration of py_edge_refine (edge_refine/examples/edge_refine.cpp:68-173:
  *                      cv::findContours of the rendered silhouette, the nearest-contour match, the
  *                      6 x 6 normal equations and the pose update), on zp_render's depth
+ *   zp_scene_depth, zp_gt_info
+ *                      the files the loader reads beside the GT code images: the mask_visib PNGs and
+ *                      scene_gt_info.json (bbox_visib: bop_dataset_pytorch.py:249, 411; visib_fract:
+ *                      tools_for_BOP/bop_io.py:71-72, 269-270), with the visibility test of
+ *                      lib/pysixd/visibility.py:29-36 ('bop19' and 'bop18')
  */
 #ifndef ZP_H_
 #define ZP_H_
@@ -540,6 +545,62 @@ long long zp_vsd_ws_bytes(int B, int H, int W, int ntau);
 int zp_vsd(int B, const float* depth_est, const float* depth_gt, const float* depth_test, int n_test,
            const int* test_index, int H, int W, const double* K, double delta, const double* taus, int ntau,
            const double* diameter, double* out, int* counts, void* ws, void* stream);
+
+/* ---- BOP GT masks and info -----------------------------------------------------------------
+ * The visible mask of every instance (the mask_visib PNGs) and the entries of scene_gt_info.json, which
+ * the reference's loader reads (bop_dataset_pytorch.py:249, 411: bbox_visib; tools_for_BOP/bop_io.py:
+ * 71-72, 269-270 and lib/pysixd/scripts/eval_calc_scores.py:215: visib_fract) and which in a BOP
+ * dataset come from the BOP toolkit's calc_gt_masks.py / calc_gt_info.py.  The toolkit is not part
+ * of the reference: for px_count_all, the large render and the empty-box rule the text below is the
+ * specification.  tests/gtinfo_ref.py restates both functions in numpy; the outputs match it exactly.
+ *
+ * zp_scene_depth: the depth image of each of n_img synthetic scenes from its instances' renders.
+ *   depth f32 [B][H][W]: zp_render's camera Z, 0 = no surface; img_index i32 [B] (device): the image
+ *   instance b belongs to, in any order, several instances per image; an index outside [0, n_img)
+ *   contributes nothing.
+ *   scene f32 [n_img][H][W] = the smallest depth > 0 over the image's instances, 0 where there is none;
+ *   instance i32 [n_img][H][W] (may be NULL) = the b that supplied it, the lowest b on a tie, -1 for
+ *   background.  A gather over the instances in ascending b: no atomics and no workspace, bitwise
+ *   reproducible, independent of the order the instances are listed in (up to the names b).
+ *   1 <= B, n_img <= 65535, H, W >= 1, H * W < 2^31 - 1024.
+ *
+ * zp_gt_info: per-instance masks, pixel counts and boxes.
+ *   depth_gt f32 [B][Hg][Wg]: instance b rendered alone.  The window [oy, oy + H) x [ox, ox + W) of it
+ *   is the image; the rest is the part of the object outside the frame (the toolkit renders at 3 H x
+ *   3 W with the principal point moved by (W, H); Hg x Wg = H x W with a zero origin is allowed).
+ *   depth_test f32 [n_test][H][W]: the scene's depth, measured or from zp_scene_depth, in the unit of
+ *   the poses; test_index i32 [B] or NULL, as in zp_vsd (out-of-range entries are read as the nearest
+ *   valid one; NULL: image b, then n_test >= B).  K f64 [B][4] = (fx, fy, cx, cy) of the IMAGE, not
+ *   the shifted ones of the large render.
+ *   Outputs (each may be NULL): mask u8 [B][H][W] (255 / 0) = depth_gt > 0 in the window; mask_visib
+ *   u8 [B][H][W] (255 / 0); info i32 [B][11] = px_count_all, px_count_valid, px_count_visib, obj_x0,
+ *   obj_y0, obj_x1, obj_y1, vis_x0, vis_y0, vis_x1, vis_y1.
+ *   Distance image (misc.py:571-590) of the window of depth_gt and of depth_test at window pixel
+ *   (x, y), exactly zp_vsd's: pX = (x - cx) / fx, pY = (y - cy) / fy, z = f64(d),
+ *   dist = sqrt(((pX z)^2 + (pY z)^2) + z^2), every step one IEEE f64 operation.
+ *   Visibility (visibility.py:29-36), diff = f32(dist_gt) - f32(dist_test):
+ *     ZP_VISIB_BOP19: (diff <= f32(delta) || dist_test == 0) && dist_gt > 0
+ *     ZP_VISIB_BOP18:  diff <= f32(delta) && dist_test > 0 && dist_gt > 0
+ *   px_count_all   = #(depth_gt > 0) over the WHOLE Hg x Wg render (the truncated part counts, which
+ *                    is why visib_fract falls for an object that leaves the frame);
+ *   px_count_valid = #(dist_gt > 0 && dist_test > 0) over the window;
+ *   px_count_visib = #(visible) over the window.
+ *   obj_* = inclusive min / max corners of depth_gt > 0 over the whole render in image coordinates
+ *   (render coordinate minus (ox, oy): they can be negative or exceed the frame); vis_* = the same of
+ *   the visible mask.  A box with no pixels is (-1, -1, -1, -1).
+ *   Every counter and corner is an integer merged with integer add / min / max (registers -> wave ->
+ *   LDS -> one atomic per workgroup and counter), so the output is exact and independent of the order
+ *   of the pixels.
+ * 1 <= B <= 65535, Hg * Wg < 2^31 - 1024, 0 <= ox, ox + W <= Wg, 0 <= oy, oy + H <= Hg, n_test >= 1;
+ * anything else, an unknown visib_mode, or a NULL depth_gt / depth_test / K is ZP_ERR_ARG before any
+ * device call. */
+#define ZP_VISIB_BOP19 0
+#define ZP_VISIB_BOP18 1
+int zp_scene_depth(int B, const float* depth, const int* img_index, int n_img, int H, int W, float* scene,
+                   int* instance, void* stream);
+int zp_gt_info(int B, const float* depth_gt, int Hg, int Wg, int ox, int oy, int H, int W, const float* depth_test,
+               int n_test, const int* test_index, const double* K, double delta, int visib_mode, uint8_t* mask,
+               uint8_t* mask_visib, int* info, void* stream);
 
 /* ---- device crop pipeline --------------------------------------------
  * Replaces the DataLoader worker's crop_square_resize (bop_dataset_pytorch.py:36-72) of the image

@@ -130,6 +130,8 @@ _SIGS = {
     "zp_pose_error_sym": (i32, [i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
     "zp_vsd_ws_bytes": (i64, [i32, i32, i32, i32]),
     "zp_vsd": (i32, [i32, vp, vp, vp, i32, vp, i32, i32, vp, f64, C.POINTER(f64), i32, vp, vp, vp, vp, vp]),
+    "zp_scene_depth": (i32, [i32, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "zp_gt_info": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, f64, i32, vp, vp, vp, vp]),
     "zp_crop_image": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
     "zp_crop_gt": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "zp_pack_digits": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
