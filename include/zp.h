@@ -34,6 +34,9 @@
  *                      common_ops.py:21-28, class_id_encoder_decoder.py:17-28, 43-63)
  *   zp_augment         apply_augmentation (bop_dataset_pytorch.py:349-355): the imgaug colour chain of
  *                      GDR_Net_Augmentation.py:161-178 ahead of the is_train crop (:267-277)
+ *   zp_crop_image_m, zp_crop_gt_m, zp_augment_m
+ *                      the crops with resize_method "crop_square_resize" (bop_dataset_pytorch.py:36-72) or
+ *                      "crop_resize" (:74-88, the paper and ablation configs)
  *   zp_adam            torch.optim.Adam step used by train_v6.py:268-269, 338
  *   zp_render          the OpenGL GT renderer Binary_Code_GT_Generator/Render_GT_Color_Mesh_to_GT_Img
  *                      (render_related_source/opengl_render.cpp:164-206, camera.hpp:29-59,
@@ -619,6 +622,28 @@ int zp_crop_image(const uint8_t* imgs, int n_img, int H, int W, const int* img_i
 int zp_crop_gt(const uint8_t* gts, const uint8_t* masks, const uint8_t* entire_masks, int n_img, int H, int W,
                const int* img_index, const int* bbox, int B, int S, int L, uint8_t* code, float* mask_out,
                float* entire_out, void* stream);
+/* The same with the reference's resize_method as an argument (zp_crop_image / zp_crop_gt / zp_augment are
+ * the ZP_CROP_SQUARE case, bit for bit):
+ *   ZP_CROP_SQUARE  "crop_square_resize" (bop_dataset_pytorch.py:36-72; the config_BOP files): as above.
+ *   ZP_CROP_RECT    "crop_resize" (:74-88; the paper and ablation configs): the ROI is the box clipped to
+ *                   the image, x1 = max(0, x), x2 = min(W, x + w), y1 = max(0, y), y2 = min(H, y + h), an
+ *                   sw x sh = (x2 - x1) x (y2 - y1) slice with no squaring and no zero fill, resized to
+ *                   S x S with one scale per axis (1 / (S / sw), 1 / (S / sh)): INTER_LINEAR's taps with
+ *                   n = sw for x and n = sh for y; the 2 x 2 box filter only when both scales are exactly
+ *                   2, a copy only when sw == sh == S; INTER_NEAREST per axis.  get_final_Bbox(..,
+ *                   "crop_resize") (:183-192) returns that clipped box.
+ * Deviation from the reference: an empty ROI under ZP_CROP_RECT (sw <= 0 or sh <= 0: w <= 0, h <= 0 or a box
+ * wholly outside the image), on which cv2.resize raises (and for x + w < 0 the reference's slice wraps
+ * around), gives the all-zero dummy crop (x = 0.0, code = 0, masks = 0), and zp_augment_m writes nothing.
+ * Parity of the resize with OpenCV itself is unpinned for both methods (tests/crop_rect_ref.py,
+ * oracle/crop_ref.py restate it).  Any other method is ZP_ERR_ARG before any device call. */
+#define ZP_CROP_SQUARE 0
+#define ZP_CROP_RECT 1
+int zp_crop_image_m(const uint8_t* imgs, int n_img, int H, int W, const int* img_index, const int* bbox, int B, int S,
+                    float* out, int method, void* stream);
+int zp_crop_gt_m(const uint8_t* gts, const uint8_t* masks, const uint8_t* entire_masks, int n_img, int H, int W,
+                 const int* img_index, const int* bbox, int B, int S, int L, uint8_t* code, float* mask_out,
+                 float* entire_out, int method, void* stream);
 /* GT digit planes of a d-ary code, d = 2^s: bits u8 [B][nbits][H][W] (zp_crop_gt's planes, channel 0 =
  * MSB) -> digits u8 [B][nbits/s][H][W], digit_i = planes [s*i, s*i+s) read MSB first -- with nbits = 16
  * the reference's class_id_image_to_class_code_images(id, d, 16/s, 65536)
@@ -659,6 +684,12 @@ typedef struct {
 int zp_augment(const uint8_t* imgs, int n_img, int H, int W, const int* img_index, const zp_aug_desc* desc,
                const uint8_t* masks, int mh, int mw, const uint8_t* luts, const uint8_t* beta_tab, const int* bbox,
                int B, uint8_t* out, void* stream);
+/* zp_augment with the crop method the box is read with (ZP_CROP_SQUARE / ZP_CROP_RECT above).  Under
+ * ZP_CROP_RECT the written tiles are those meeting the clipped box [x1, x2) x [y1, y2); an empty one
+ * writes nothing. */
+int zp_augment_m(const uint8_t* imgs, int n_img, int H, int W, const int* img_index, const zp_aug_desc* desc,
+                 const uint8_t* masks, int mh, int mw, const uint8_t* luts, const uint8_t* beta_tab, const int* bbox,
+                 int B, uint8_t* out, int method, void* stream);
 
 /* ---- GT renderer ------------------------------------------------------------------------
  * B renders of one mesh (GT code images, depth, masks), replacing the reference's OpenGL program

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("ZP_LIB", os.path.join(_HERE, "libzp.so"))
 ZP_F32, ZP_BF16, ZP_F16, ZP_F32X3, ZP_F32H2 = 0, 1, 2, 3, 4
 ZP_OUT_NHWC, ZP_OUT_HEAD_NCHW, ZP_OUT_NHWC_F32, ZP_OUT_NHWC_X3, ZP_OUT_NHWC_H2 = 0, 1, 2, 3, 4
 MAX_TAPS, MAX_SUB = 64, 4
+ZP_CROP_SQUARE, ZP_CROP_RECT = 0, 1
 
 vp = C.c_void_p
 i32 = C.c_int
@@ -136,6 +137,9 @@ _SIGS = {
     "zp_crop_gt": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "zp_pack_digits": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
     "zp_augment": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp]),
+    "zp_crop_image_m": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp]),
+    "zp_crop_gt_m": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp]),
+    "zp_augment_m": (i32, [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, i32, vp]),
     "zp_adam_multi": (i32, [i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, i64, vp]),
     "zp_adam_multi_dev": (i32, [i32, vp, vp, vp, vp, vp, f64, f64, f64, f64, vp, vp]),
     "zp_split_range_flag": (i32, [vp]),

@@ -253,11 +253,12 @@ def _pack(batch: AugBatch):
     return buf, offs
 
 
-def augment_images(images, img_index, batch: AugBatch, bbox=None, out=None):
-    """``zp_augment``: images u8 [N, H, W, 3] (BGR, device), img_index int [B] (host or device int32),
+def augment_images(images, img_index, batch: AugBatch, bbox=None, out=None, method=L.ZP_CROP_SQUARE):
+    """``zp_augment_m``: images u8 [N, H, W, 3] (BGR, device), img_index int [B] (host or device int32),
     bbox None or int32 [B, 4] (host or device) -> u8 [B, H, W, 3].  With ``bbox`` only the tiles
     meeting each crop's copied region are written; the rest of ``out`` keeps its contents
-    (uninitialised when ``out`` is not given)."""
+    (uninitialised when ``out`` is not given).  ``method`` (``ZP_CROP_SQUARE`` / ``ZP_CROP_RECT``) is
+    the crop method that will read ``bbox``: the squared box or the box clipped to the image."""
     if not (isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and images.is_cuda and images.dim() == 4
             and images.shape[3] == 3):
         raise ValueError("images: expected a uint8 CUDA tensor [N, H, W, 3]")
@@ -289,7 +290,7 @@ def augment_images(images, img_index, batch: AugBatch, bbox=None, out=None):
     buf, offs = _pack(batch)
     dbuf = torch.from_numpy(buf).to(dev)
     base = dbuf.data_ptr()
-    L.call("zp_augment", images.data_ptr(), N, H, W, ii.data_ptr(), base + offs[0], base + offs[1], mh, mw,
-           base + offs[2], base + offs[3], L.ptr(bb), B, out.data_ptr(), L.stream_ptr())
+    L.call("zp_augment_m", images.data_ptr(), N, H, W, ii.data_ptr(), base + offs[0], base + offs[1], mh, mw,
+           base + offs[2], base + offs[3], L.ptr(bb), B, out.data_ptr(), int(method), L.stream_ptr())
     dbuf.record_stream(torch.cuda.current_stream(dev))
     return out

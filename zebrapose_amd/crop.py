@@ -8,8 +8,14 @@ image and masks), turns the GT colours into 16 code planes (``RGB_image_to_class
 ``class_id_image_to_class_code_images``), normalises the image (``transform_pre``) and returns
 ``get_final_Bbox``'s box.  Here the box arithmetic stays on the host (a few integer operations
 per crop, same functions as the reference) and the pixel work is two kernels over a whole batch
-(``zp_crop_image``, ``zp_crop_gt``, csrc/zp_crop.hip) reading images resident in HBM.
-Only ``resize_method="crop_square_resize"`` (the configs' method) is on the device.
+(``zp_crop_image_m``, ``zp_crop_gt_m``, csrc/zp_crop.hip) reading images resident in HBM.
+Two of the reference's three ``resize_method``s are on the device: ``"crop_square_resize"`` (the
+``config_BOP`` files; the default) and ``"crop_resize"`` (:74-88; every ``config_paper`` and
+``config_ablation`` file): the box clipped to the image, sliced without squaring or zero padding
+and resized with one scale per axis.  ``"crop_resize_by_warp_affine"``, which no config selects,
+is not.  An empty clipped box, on which the reference's ``cv2.resize`` raises, is handled like a
+missing detection (zero boxes, the all-zero dummy crop).  Parity of the resize with OpenCV itself
+is unpinned for both methods (oracle/crop_ref.py, tests/crop_rect_ref.py restate it).
 
 ``CropPipeline.train_batch`` is the ``is_train`` branch (:267-277): ``aug_Bbox`` jitters the box
 on the host, ``zp_augment`` (augment.py) runs the imgaug colour chain over the part of the image
@@ -77,13 +83,24 @@ def _u8(t, name, ndim):
 
 
 class CropPipeline:
-    """Batched square-ROI crops of device-resident images (``crop_square_resize`` path)."""
+    """Batched crops of device-resident images: square ROIs (``crop_square_resize``) or the clipped
+    rectangular ones of ``crop_resize``."""
+
+    _METHODS = {"crop_square_resize": L.ZP_CROP_SQUARE, "crop_resize": L.ZP_CROP_RECT}
 
     def __init__(self, crop_size_img=256, crop_size_gt=128, code_bits=16, padding_ratio=1.5, class_base=2,
-                 iterations=None):
+                 iterations=None, resize_method="crop_square_resize"):
         """class_base d != 2 (the d-ary code ablation): ``code`` holds the ``iterations`` digit planes
         of class_id_image_to_class_code_images(id, d, iterations, 65536)
-        (class_id_encoder_decoder.py:43-63; iterations defaults to log_d 65536)."""
+        (class_id_encoder_decoder.py:43-63; iterations defaults to log_d 65536).
+        resize_method: the config key of that name, ``"crop_square_resize"`` or ``"crop_resize"``."""
+        if resize_method == "crop_resize_by_warp_affine":
+            raise NotImplementedError("resize_method crop_resize_by_warp_affine is not on the device (no config "
+                                      "selects it); use crop_square_resize or crop_resize")
+        if resize_method not in self._METHODS:
+            raise NotImplementedError(f"unknown decoder type: {resize_method}")  # get_roi (:122)
+        self.resize_method = resize_method
+        self.method = self._METHODS[resize_method]
         self.S_img, self.S_gt = int(crop_size_img), int(crop_size_gt)
         self.L = int(code_bits)
         self.padding_ratio = padding_ratio
@@ -104,17 +121,25 @@ class CropPipeline:
     def boxes(self, Bboxes, img_w, img_h):
         """Host box arithmetic for a batch of raw boxes [B, 4] -> (padded boxes int32 [B, 4] fed to
         the kernels, final boxes int64 [B, 4] for the decode).  A box of -1s (no detection) stays a
-        zero box: the kernels then emit the reference's all-zero dummy crop."""
+        zero box: the kernels then emit the reference's all-zero dummy crop.  So does, under
+        ``"crop_resize"``, a box whose clipped ROI is empty."""
         pad, fin = [], []
         for bb in np.asarray(Bboxes).reshape(-1, 4):
             if np.any(np.isclose(bb, -1)):  # :291-298
                 pad.append(np.zeros(4, np.int64))
                 fin.append(np.zeros(4, np.int64))
                 continue
-            p = padding_Bbox(bb, self.padding_ratio)
+            p, f = self._final(padding_Bbox(bb, self.padding_ratio), img_w, img_h)
             pad.append(p)
-            fin.append(get_final_Bbox(p, "crop_square_resize", img_w, img_h))
+            fin.append(f)
         return np.stack(pad).astype(np.int32), np.stack(fin).astype(np.int64)
+
+    def _final(self, box, img_w, img_h):
+        """(box, get_final_Bbox of it); two zero boxes when ``crop_resize`` clips the box to nothing."""
+        f = get_final_Bbox(box, self.resize_method, img_w, img_h)
+        if self.method == L.ZP_CROP_RECT and (f[2] <= 0 or f[3] <= 0):
+            return np.zeros(4, np.int64), np.zeros(4, np.int64)
+        return box, f
 
     def __call__(self, images, img_index, boxes, gt_images=None, masks=None, entire_masks=None):
         """images u8 [N, H, W, 3] (BGR, device); img_index int [B]; boxes = padded boxes int [B, 4].
@@ -148,16 +173,16 @@ class CropPipeline:
         dev = images.device
         st = L.stream_ptr()
         out = {"x": torch.empty((B, 3, self.S_img, self.S_img), dtype=torch.float32, device=dev)}
-        L.call("zp_crop_image", images.data_ptr(), N, H, W, ii.data_ptr(), bb.data_ptr(), B, self.S_img,
-               out["x"].data_ptr(), st)
+        L.call("zp_crop_image_m", images.data_ptr(), N, H, W, ii.data_ptr(), bb.data_ptr(), B, self.S_img,
+               out["x"].data_ptr(), self.method, st)
         if gt_images is not None or masks is not None or entire_masks is not None:
             S = self.S_gt
             Ng = next(t for t in (gt_images, masks, entire_masks) if t is not None).shape[0]
             code = torch.empty((B, self.L, S, S), dtype=torch.uint8, device=dev) if gt_images is not None else None
             m = torch.empty((B, S, S), dtype=torch.float32, device=dev) if masks is not None else None
             e = torch.empty((B, S, S), dtype=torch.float32, device=dev) if entire_masks is not None else None
-            L.call("zp_crop_gt", L.ptr(gt_images), L.ptr(masks), L.ptr(entire_masks), Ng, H, W, gt_ii.data_ptr(),
-                   bb.data_ptr(), B, S, self.L, L.ptr(code), L.ptr(m), L.ptr(e), st)
+            L.call("zp_crop_gt_m", L.ptr(gt_images), L.ptr(masks), L.ptr(entire_masks), Ng, H, W, gt_ii.data_ptr(),
+                   bb.data_ptr(), B, S, self.L, L.ptr(code), L.ptr(m), L.ptr(e), self.method, st)
             if code is not None and self.digit_bits:  # the 16 bit planes -> 16 / s digit planes (zp_pack_digits)
                 digits = torch.empty((B, 16 // self.digit_bits, S, S), dtype=torch.uint8, device=dev)
                 L.call("zp_pack_digits", code.data_ptr(), B, 16, S, S, self.digit_bits, digits.data_ptr(), st)
@@ -169,9 +194,9 @@ class CropPipeline:
         """``boxes`` for the training branch: aug_Bbox in place of padding_Bbox (:270, :277)."""
         aug, fin = [], []
         for bb in np.asarray(Bboxes).reshape(-1, 4):
-            a = aug_Bbox(bb, self.padding_ratio, rng)
+            a, f = self._final(aug_Bbox(bb, self.padding_ratio, rng), img_w, img_h)
             aug.append(a)
-            fin.append(get_final_Bbox(a, "crop_square_resize", img_w, img_h))
+            fin.append(f)
         return np.stack(aug).astype(np.int32), np.stack(fin).astype(np.int64)
 
     def train_batch(self, images, img_index, raw_boxes, gt_images, masks, entire_masks, sampler):
@@ -190,7 +215,7 @@ class CropPipeline:
             raise ValueError("raw_boxes and img_index disagree on the batch size")
         batch = sampler.sample(B, H, W)
         bb = torch.from_numpy(aug_boxes).to(images.device)
-        aug = augment_images(images, ii, batch, bbox=bb)
+        aug = augment_images(images, ii, batch, bbox=bb, method=self.method)
         out = self._crop(aug, torch.arange(B, dtype=torch.int32, device=images.device), bb, gt_images, masks,
                          entire_masks, ii)
         out.update(final_boxes=final_boxes, boxes=aug_boxes, aug=batch)

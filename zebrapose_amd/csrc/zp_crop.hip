@@ -1,23 +1,31 @@
-// Device-side crop pipeline: square ROI crop + resize + normalisation of the
+// Device-side crop pipeline: ROI crop + resize + normalisation of the
 // RGB input, nearest-neighbour crops of the GT code image and the masks, GT colour -> 16-bit
 // code planes.  Replaces the CPU DataLoader worker path of bop_dataset_pytorch.py:
-//   padding_Bbox (:124-139, host) -> get_roi(.., "crop_square_resize") (:36-72, :110-122)
-//   with cv2.INTER_LINEAR (image, 256) / cv2.INTER_NEAREST (GT image, masks, 128) (:311-316)
+//   padding_Bbox (:124-139, host) -> get_roi (:110-122) with one of two resize_methods,
+//     ZP_CROP_SQUARE  "crop_square_resize" (:36-72, the config_BOP files): the box squared around its
+//                     centre, a zero-padded s x s ROI
+//     ZP_CROP_RECT    "crop_resize" (:74-88, the paper and ablation configs): the box clipped to the
+//                     image, an sw x sh ROI wholly inside it, each axis resized with its own scale
+//     (crop_resize_by_warp_affine, which no config selects, is not on the device)
+//   with cv2.INTER_LINEAR (image, 256) / cv2.INTER_NEAREST (GT image, masks, 128) (:304-316)
 //   -> RGB_image_to_class_id_image + class_id_image_to_class_code_images
 //      (class_id_encoder_decoder.py:6-15, 43-63) -> transform_pre (:333-347: ToTensor +
 //      Normalize with the RGB ImageNet constants on the BGR array, masks / 255.)
 // cv2.resize is a third-party dependency absent from the image; the resize arithmetic follows
-// OpenCV 4.x's generic (non-IPP) path, restated in oracle/crop_ref.py (parity vs OpenCV unpinned):
+// OpenCV 4.x's generic (non-IPP) path, restated in oracle/crop_ref.py for a square source and in
+// tests/crop_rect_ref.py per axis (parity vs OpenCV unpinned for both methods); below, n is the ROI's
+// side along the axis (sw for x, sh for y) and scale = 1 / (dsize / n):
 //   INTER_LINEAR, 8U: fx = (float)((dx + 0.5) * scale - 0.5), sx = floor(fx), clamped at both
 //     borders with fx = 0; 11-bit fixed-point coefficients saturate_cast<short>(c * 2048);
 //     horizontal pass exact in int32; vertical pass as the SIMD kernel computes it:
-//     u8((mulhi16(h0 >> 4, b0) + mulhi16(h1 >> 4, b1) + 2) >> 2); an exact 2x downscale is
-//     routed to INTER_AREA (2x2 box, (a + b + c + d + 2) >> 2) as cv::resize does.
+//     u8((mulhi16(h0 >> 4, b0) + mulhi16(h1 >> 4, b1) + 2) >> 2); an exact 2x downscale of BOTH axes
+//     is routed to INTER_AREA (2x2 box, (a + b + c + d + 2) >> 2) as cv::resize does; sw == sh == S copies.
 //   INTER_NEAREST: sx = min(floor(dx * (1 / (dsize / ssize))), ssize - 1).
 // One thread per output pixel; the source image stays in HBM/L2 (one crop reads at most its
 // ROI once), outputs are written coalesced.
 // The training branch's colour augmentation (apply_augmentation, :349-355) runs ahead of the image
 // crop as one fused tile kernel (k_augment below, zp_augment), sharing crop_geo with the crops.
+// An empty ROI (either side <= 0; cv2.resize raises on it) is the all-zero dummy crop under both methods.
 #include <math.h>
 #include "zp_common.h"
 
@@ -25,14 +33,25 @@ namespace zp {
 
 struct CropGeo {
   int x1, y1, xe, ye;  // ROI origin in the image, exclusive end of the copied image region
-  int s;               // ROI side (max(bh, bw)); 0 = dummy crop
+  int sw, sh;          // ROI sides; both 0 = dummy crop
 };
 
-// crop_square_resize (:36-72): square-ify around the box centre, int() truncation, the ROI is
-// s x s with roi(y, x) = img(y1 + y, x1 + x) inside [0, min(H, y2)) x [0, min(W, x2)), else 0
-__device__ __forceinline__ CropGeo crop_geo(const int* bb, int H, int W) {
+// ZP_CROP_RECT, crop_resize (:74-88): the box clipped to the image is the ROI, every pixel of it in the image.
+// ZP_CROP_SQUARE, crop_square_resize (:36-72): square-ify around the box centre, int() truncation, the ROI is
+// s x s (s = max(bh, bw)) with roi(y, x) = img(y1 + y, x1 + x) inside [0, min(H, y2)) x [0, min(W, x2)), else 0
+__device__ __forceinline__ CropGeo crop_geo(const int* bb, int H, int W, int method) {
   CropGeo g;
   const int bx = bb[0], by = bb[1];
+  if (method == ZP_CROP_RECT) {
+    g.x1 = max(bx, 0);
+    g.y1 = max(by, 0);
+    g.xe = (int)max(min((long long)bx + bb[2], (long long)W), 0ll);  // 64-bit sum: no wrap for any int32 box
+    g.ye = (int)max(min((long long)by + bb[3], (long long)H), 0ll);
+    g.sw = g.xe - g.x1;
+    g.sh = g.ye - g.y1;
+    if (g.sw <= 0 || g.sh <= 0) g.sw = g.sh = 0;
+    return g;
+  }
   const int bw = max(bb[2], 0), bh = max(bb[3], 0);
   double x1 = bx, x2 = (double)bx + bw, y1 = by, y2 = (double)by + bh;
   const double cx = 0.5 * (x1 + x2), cy = 0.5 * (y1 + y2);
@@ -47,7 +66,7 @@ __device__ __forceinline__ CropGeo crop_geo(const int* bb, int H, int W) {
   g.y1 = (int)y1;
   g.xe = min((int)x2, W);
   g.ye = min((int)y2, H);
-  g.s = max(bh, bw);
+  g.sw = g.sh = max(bh, bw);
   return g;
 }
 
@@ -90,6 +109,12 @@ __device__ __forceinline__ LinTap lin_tap(int d, double scale, int n) {
   return t;
 }
 
+// cv::resize's is_area_fast test for a scale of 2: within DBL_EPSILON of the integer
+__device__ __forceinline__ bool exactly_2x(double scale) {
+  const int iscale = (int)rint(scale);
+  return iscale == 2 && fabs(scale - iscale) < 2.220446049250313e-16;
+}
+
 __device__ __forceinline__ int mulhi16(int a, int b) {
   a = max(-32768, min(32767, a));  // v_pack saturation
   return (a * b) >> 16;
@@ -98,32 +123,33 @@ __device__ __forceinline__ int mulhi16(int a, int b) {
 // image crop: out f32 NCHW [B][3][S][S], normalised ((v / 255 - mean[c]) / std[c], BGR order kept)
 __global__ void __launch_bounds__(256) k_crop_image(const uint8_t* __restrict__ imgs, int H, int W,
                                                     const int* __restrict__ img_index, const int* __restrict__ bbox,
-                                                    int S, float* __restrict__ out) {
+                                                    int S, float* __restrict__ out, int method) {
   const int b = blockIdx.y;
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= S * S) return;
   const int dy = p / S, dx = p - dy * S;
-  const CropGeo g = crop_geo(bbox + 4 * b, H, W);
+  const CropGeo g = crop_geo(bbox + 4 * b, H, W, method);
   const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
   float* o = out + (size_t)b * 3 * S * S + p;
-  if (g.s <= 0) {  // the reference's dummy input for a missing detection (:285-298): zeros
+  if (g.sw <= 0) {  // the reference's dummy input for a missing detection (:285-298): zeros
     for (int c = 0; c < 3; ++c) o[(size_t)c * S * S] = 0.f;
     return;
   }
   const uint8_t* img = imgs + (size_t)img_index[b] * H * W * 3;
   int v[3];
-  const double inv = (double)S / g.s;  // cv::resize: inv_scale = dsize / ssize, scale = 1 / inv_scale
-  const double scale = 1.0 / inv;
-  const int iscale = (int)rint(scale);
-  if (g.s == S) {
+  // cv::resize per axis: inv_scale = dsize / ssize, scale = 1 / inv_scale
+  // (equal sides, always so for ZP_CROP_SQUARE, share one pair of f64 divisions)
+  const double scale_x = 1.0 / ((double)S / g.sw);
+  const double scale_y = g.sh == g.sw ? scale_x : 1.0 / ((double)S / g.sh);
+  if (g.sw == S && g.sh == S) {
     for (int c = 0; c < 3; ++c) v[c] = roi_px(img, W, g, dy, dx, c);
-  } else if (iscale == 2 && fabs(scale - iscale) < 2.220446049250313e-16) {
-    // INTER_LINEAR at an exact 2x downscale -> INTER_AREA fast path (2 x 2 box)
+  } else if (exactly_2x(scale_x) && exactly_2x(scale_y)) {
+    // INTER_LINEAR at an exact 2x downscale of both axes -> INTER_AREA fast path (2 x 2 box)
     for (int c = 0; c < 3; ++c)
       v[c] = (roi_px(img, W, g, 2 * dy, 2 * dx, c) + roi_px(img, W, g, 2 * dy, 2 * dx + 1, c) +
               roi_px(img, W, g, 2 * dy + 1, 2 * dx, c) + roi_px(img, W, g, 2 * dy + 1, 2 * dx + 1, c) + 2) >> 2;
   } else {
-    const LinTap tx = lin_tap(dx, scale, g.s), ty = lin_tap(dy, scale, g.s);
+    const LinTap tx = lin_tap(dx, scale_x, g.sw), ty = lin_tap(dy, scale_y, g.sh);
     for (int c = 0; c < 3; ++c) {
       int h[2];
       for (int k = 0; k < 2; ++k) {
@@ -147,16 +173,17 @@ __global__ void __launch_bounds__(256) k_crop_gt(const uint8_t* __restrict__ gts
                                                  const uint8_t* __restrict__ entire, int H, int W,
                                                  const int* __restrict__ img_index, const int* __restrict__ bbox, int S,
                                                  int L, uint8_t* __restrict__ code, float* __restrict__ mask_out,
-                                                 float* __restrict__ entire_out) {
+                                                 float* __restrict__ entire_out, int method) {
   const int b = blockIdx.y;
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= S * S) return;
   const int dy = p / S, dx = p - dy * S;
-  const CropGeo g = crop_geo(bbox + 4 * b, H, W);
+  const CropGeo g = crop_geo(bbox + 4 * b, H, W, method);
   int id = 0, mv = 0, ev = 0;
-  if (g.s > 0) {
-    const double ifx = 1.0 / ((double)S / g.s);
-    const int sx = min((int)floor(dx * ifx), g.s - 1), sy = min((int)floor(dy * ifx), g.s - 1);
+  if (g.sw > 0) {
+    const double ifx = 1.0 / ((double)S / g.sw);
+    const double ify = g.sh == g.sw ? ifx : 1.0 / ((double)S / g.sh);
+    const int sx = min((int)floor(dx * ifx), g.sw - 1), sy = min((int)floor(dy * ify), g.sh - 1);
     const int iy = g.y1 + sy, ix = g.x1 + sx;
     if (iy >= 0 && ix >= 0 && iy < g.ye && ix < g.xe) {
       const size_t im = (size_t)img_index[b] * H * W;
@@ -241,16 +268,17 @@ __global__ void __launch_bounds__(256) k_augment(const uint8_t* __restrict__ img
                                                  const int* __restrict__ img_index, const AugDesc* __restrict__ desc,
                                                  const uint8_t* __restrict__ masks, int mh, int mw,
                                                  const uint8_t* __restrict__ luts, const uint8_t* __restrict__ beta_tab,
-                                                 const int* __restrict__ bbox, uint8_t* __restrict__ out, int vec) {
+                                                 const int* __restrict__ bbox, uint8_t* __restrict__ out, int vec,
+                                                 int method) {
   __shared__ uint32_t p0[AUG_P0 * AUG_P0];
   __shared__ uint32_t p1[AUG_P1 * AUG_P1];
   __shared__ uint32_t obuf[AUG_T * AUG_T * 3 / 4];
   __shared__ uint8_t lut_s[3 * 256];
   __shared__ int mrow[AUG_P1], mcol[AUG_P1];
   const int b = blockIdx.z, ty0 = blockIdx.y * AUG_T, tx0 = blockIdx.x * AUG_T, tid = threadIdx.x;
-  if (bbox) {  // only tiles meeting the region crop_square_resize copies: [max(x1,0), xe) x [max(y1,0), ye)
-    const CropGeo g = crop_geo(bbox + 4 * b, H, W);
-    if (g.s <= 0 || tx0 >= g.xe || ty0 >= g.ye || tx0 + AUG_T <= max(g.x1, 0) || ty0 + AUG_T <= max(g.y1, 0)) return;
+  if (bbox) {  // only tiles meeting the region the crop copies: [max(x1,0), xe) x [max(y1,0), ye)
+    const CropGeo g = crop_geo(bbox + 4 * b, H, W, method);
+    if (g.sw <= 0 || tx0 >= g.xe || ty0 >= g.ye || tx0 + AUG_T <= max(g.x1, 0) || ty0 + AUG_T <= max(g.y1, 0)) return;
   }
   const AugDesc* d = desc + b;
   const uint32_t flags = d->flags;
@@ -340,28 +368,45 @@ __global__ void __launch_bounds__(256) k_augment(const uint8_t* __restrict__ img
 
 using namespace zp;
 
-extern "C" int zp_crop_image(const uint8_t* imgs, int n_img, int H, int W, const int* img_index, const int* bbox,
-                             int B, int S, float* out, void* stream) {
+#define ZP_CHECK_METHOD(fn) \
+  ZP_CHECK_ARG(method == ZP_CROP_SQUARE || method == ZP_CROP_RECT, fn ": unknown crop method %d", method)
+
+extern "C" int zp_crop_image_m(const uint8_t* imgs, int n_img, int H, int W, const int* img_index, const int* bbox,
+                               int B, int S, float* out, int method, void* stream) {
+  ZP_CHECK_METHOD("zp_crop_image_m");
   ZP_CHECK_ARG(imgs && img_index && bbox && out && n_img > 0 && H > 0 && W > 0 && B > 0 && S > 0,
                "zp_crop_image: bad args");
   ZP_CHECK_ARG((long long)n_img * H * W * 3 < (1ll << 40), "zp_crop_image: image stack too large");
   hipLaunchKernelGGL(k_crop_image, dim3((S * S + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, imgs, H, W,
-                     img_index, bbox, S, out);
+                     img_index, bbox, S, out, method);
   ZP_LAUNCH_CHECK("zp_crop_image");
+  return ZP_OK;
+}
+
+extern "C" int zp_crop_image(const uint8_t* imgs, int n_img, int H, int W, const int* img_index, const int* bbox,
+                             int B, int S, float* out, void* stream) {
+  return zp_crop_image_m(imgs, n_img, H, W, img_index, bbox, B, S, out, ZP_CROP_SQUARE, stream);
+}
+
+extern "C" int zp_crop_gt_m(const uint8_t* gts, const uint8_t* masks, const uint8_t* entire_masks, int n_img, int H,
+                            int W, const int* img_index, const int* bbox, int B, int S, int L, uint8_t* code,
+                            float* mask_out, float* entire_out, int method, void* stream) {
+  ZP_CHECK_METHOD("zp_crop_gt_m");
+  ZP_CHECK_ARG(img_index && bbox && n_img > 0 && H > 0 && W > 0 && B > 0 && S > 0, "zp_crop_gt: bad args");
+  ZP_CHECK_ARG(!code || (gts && L >= 1 && L <= 24), "zp_crop_gt: code planes need the GT image and 1 <= L <= 24");
+  ZP_CHECK_ARG(!mask_out || masks, "zp_crop_gt: mask_out needs masks");
+  ZP_CHECK_ARG(!entire_out || entire_masks, "zp_crop_gt: entire_out needs entire_masks");
+  hipLaunchKernelGGL(k_crop_gt, dim3((S * S + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, gts, masks,
+                     entire_masks, H, W, img_index, bbox, S, L, code, mask_out, entire_out, method);
+  ZP_LAUNCH_CHECK("zp_crop_gt");
   return ZP_OK;
 }
 
 extern "C" int zp_crop_gt(const uint8_t* gts, const uint8_t* masks, const uint8_t* entire_masks, int n_img, int H,
                           int W, const int* img_index, const int* bbox, int B, int S, int L, uint8_t* code,
                           float* mask_out, float* entire_out, void* stream) {
-  ZP_CHECK_ARG(img_index && bbox && n_img > 0 && H > 0 && W > 0 && B > 0 && S > 0, "zp_crop_gt: bad args");
-  ZP_CHECK_ARG(!code || (gts && L >= 1 && L <= 24), "zp_crop_gt: code planes need the GT image and 1 <= L <= 24");
-  ZP_CHECK_ARG(!mask_out || masks, "zp_crop_gt: mask_out needs masks");
-  ZP_CHECK_ARG(!entire_out || entire_masks, "zp_crop_gt: entire_out needs entire_masks");
-  hipLaunchKernelGGL(k_crop_gt, dim3((S * S + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, gts, masks,
-                     entire_masks, H, W, img_index, bbox, S, L, code, mask_out, entire_out);
-  ZP_LAUNCH_CHECK("zp_crop_gt");
-  return ZP_OK;
+  return zp_crop_gt_m(gts, masks, entire_masks, n_img, H, W, img_index, bbox, B, S, L, code, mask_out, entire_out,
+                      ZP_CROP_SQUARE, stream);
 }
 
 extern "C" int zp_pack_digits(const uint8_t* bits, int B, int nbits, int H, int W, int s, uint8_t* digits, void* stream) {
@@ -376,9 +421,10 @@ extern "C" int zp_pack_digits(const uint8_t* bits, int B, int nbits, int H, int 
   return ZP_OK;
 }
 
-extern "C" int zp_augment(const uint8_t* imgs, int n_img, int H, int W, const int* img_index, const zp_aug_desc* desc,
-                          const uint8_t* masks, int mh, int mw, const uint8_t* luts, const uint8_t* beta_tab,
-                          const int* bbox, int B, uint8_t* out, void* stream) {
+extern "C" int zp_augment_m(const uint8_t* imgs, int n_img, int H, int W, const int* img_index,
+                            const zp_aug_desc* desc, const uint8_t* masks, int mh, int mw, const uint8_t* luts,
+                            const uint8_t* beta_tab, const int* bbox, int B, uint8_t* out, int method, void* stream) {
+  ZP_CHECK_METHOD("zp_augment_m");
   static_assert(sizeof(AugDesc) == sizeof(zp_aug_desc) && sizeof(zp_aug_desc) == 53 * 4, "zp_aug_desc layout");
   ZP_CHECK_ARG(imgs && img_index && desc && masks && luts && beta_tab && out, "zp_augment: null pointer");
   ZP_CHECK_ARG(n_img > 0 && B > 0 && B <= 65535, "zp_augment: bad n_img %d / B %d", n_img, B);
@@ -391,7 +437,14 @@ extern "C" int zp_augment(const uint8_t* imgs, int n_img, int H, int W, const in
   const int vec = (W * 3) % 4 == 0 && ((uintptr_t)out & 3) == 0;
   hipLaunchKernelGGL(k_augment, dim3((W + AUG_T - 1) / AUG_T, (H + AUG_T - 1) / AUG_T, B), dim3(256), 0,
                      (hipStream_t)stream, imgs, H, W, img_index, (const AugDesc*)desc, masks, mh, mw, luts, beta_tab,
-                     bbox, out, vec);
+                     bbox, out, vec, method);
   ZP_LAUNCH_CHECK("zp_augment");
   return ZP_OK;
+}
+
+extern "C" int zp_augment(const uint8_t* imgs, int n_img, int H, int W, const int* img_index, const zp_aug_desc* desc,
+                          const uint8_t* masks, int mh, int mw, const uint8_t* luts, const uint8_t* beta_tab,
+                          const int* bbox, int B, uint8_t* out, void* stream) {
+  return zp_augment_m(imgs, n_img, H, W, img_index, desc, masks, mh, mw, luts, beta_tab, bbox, B, out, ZP_CROP_SQUARE,
+                      stream);
 }
