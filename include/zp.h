@@ -43,7 +43,10 @@
  *                      shader_groundtruth.vs / .fs) driven by generate_training_labels_for_BOP_v2.py:77-85
  *   zp_mesh_code       the offline coder Binary_Code_GT_Generator/Generate_Mesh_with_GT_Color
  *                      (Generate_Mesh_with_GT_Color.cpp:61-218 balanced 2-means split, :322-455 vertex /
- *                      face ids and the class -> 3D-point LUT), binary splits only
+ *                      face ids and the class -> 3D-point LUT), binary splits
+ *   zp_mesh_code_radix the same tool run with divide_number_each_itration = 4 / 16 / 256 (the code-radix
+ *                      ablation): a balanced d-way split per level, restated (the reference balances
+ *                      classes 0 and 1 only)
  *   zp_mask_contour    the visible contour handed to the refinement (test.py:300-307: cv2.findContours
  *                      of the entire mask, the visible-mask filter, mapping_pixel_position_to_original_position)
  *   zp_edge_refine_step  one iteration of py_edge_refine (edge_refine/examples/edge_refine.cpp:68-173:
@@ -731,8 +734,8 @@ int zp_render(int B, const float* verts, int nv, const int* faces, int nf, const
  * 3D-point LUT, replacing the reference's offline tool Generate_Mesh_with_GT_Color (PCL + OpenCV):
  * `bits` levels of a balanced 2-means split of the vertices (Generate_Mesh_with_GT_Color.cpp:61-218),
  * ids with the first split as the MSB (:322-353), the face rule (:356-393) and the LUT (:396-455).
- * Binary splits only (the reference's balancing and bit assembly are 2-way; divide_number > 2 is
- * not supported).  OpenCV's k-means++ draws cannot be reproduced, so the semantics are restated in
+ * Binary splits here (the reference's balancing and bit assembly are 2-way); divide_number > 2 is
+ * zp_mesh_code_radix below.  OpenCV's k-means++ draws cannot be reproduced, so the semantics are restated in
  * exact integer arithmetic (tests/meshcode_ref.py restates them in numpy; the outputs match it bit
  * for bit and do not depend on the order of any summation):
  *   grid:     q = rint(f64(v) * 2^grid_log2) per coordinate, saturated to +-(2^19 - 1).  The host
@@ -766,6 +769,43 @@ long long zp_mesh_code_ws_bytes(int nv, int nf, int bits);
 int zp_mesh_code(const float* verts, int nv, const int* faces, int nf, int bits, int attempts, int iterations,
                  int grid_log2, long long eps2_q, const uint32_t* draws, int* vertex_ids, int* face_ids, double* lut,
                  void* ws, void* stream);
+
+/* d-ary surface codes of a raw mesh: `levels` levels of a balanced d-way split, d = divide a power of
+ * two in [4, 256] (the reference's code-radix ablation, divide_number_each_itration = 4 / 16 / 256).
+ * The reference's Divide_PointCloud_Opencv_Samesize (:61-218) calls cv::kmeans with d centres, but its
+ * "same size" step only ever moves points between classes 0 and 1 towards n / 2 (:148-214): for d > 2
+ * it is an unbalanced k-means, and cv::kmeans throws once a group holds fewer than d points.  The
+ * split is therefore restated with a real d-way balance, in exact int64 arithmetic
+ * (tests/meshcode_radix_ref.py restates it in numpy; the outputs match it bit for bit and depend on
+ * the order of no summation and of no atomic).  Grid, group order, faces and LUT are zp_mesh_code's:
+ *   level l:  (l = 0 .. levels - 1) d^l groups, the root group being all vertices, each taken in
+ *             ascending vertex index wherever an order matters; n >= d^(levels - l) vertices each.
+ *   seeds:    one uint32 draw r per (attempt, group), draws[attempt][(d^l - 1) / (d - 1) + g]: c_0 = the
+ *             group's vertex at rank (r * n) >> 32; for j = 1 .. d - 1, c_j = the group's vertex with
+ *             the largest (minimum d^2 to c_0 .. c_(j-1)), ties to the lowest vertex index
+ *             (farthest-point seeding; coincident seeds are possible among identical points).
+ *   Lloyd:    up to `iterations` steps: label = nearest centre (ties: lowest class); a non-empty
+ *             class's centre becomes floor((2 S + n_j) / (2 n_j)) per axis, an empty class keeps its
+ *             centre; the group stops after the step in which the largest of its d centre shifts^2
+ *             is <= eps2_q.  Compactness = sum of d^2 to the own centre under one more labelling;
+ *             the attempt with the lowest compactness wins (ties: lowest attempt).
+ *   balance:  (the peel) with the winning centres, D[p][j] = d^2 of vertex p to centre j and U_0 = the
+ *             group: for j = 0 .. d - 2, class j takes the k_j = floor(|U_j| / (d - j)) vertices of U_j
+ *             with the lowest D[p][j] - min_{i > j} D[p][i] (ties: lower vertex index), U_(j+1) is the
+ *             rest; class d - 1 takes U_(d-1).  Every class ends with floor(n / d) or ceil(n / d)
+ *             vertices, so no child group starves.  Children of group g: d * g + digit.
+ *   ids:      vertex id = sum_l digit_l * d^(levels - 1 - l) (the fold of zp_decode_radix and of
+ *             zp_pack_digits' planes); face ids and the LUT over d^levels classes as in zp_mesh_code.
+ * verts, faces as zp_mesh_code; draws u32 [attempts][(d^levels - 1) / (d - 1)]; outputs vertex_ids
+ * i32 [nv], face_ids i32 [nf], lut f64 [d^levels][3].  divide a power of two in [4, 256] (divide == 2
+ * is ZP_ERR_ARG: that is zp_mesh_code), levels >= 1, d^levels <= 65536, d^levels <= nv <= 2^21, nf,
+ * attempts, iterations, grid_log2 and eps2_q as zp_mesh_code; anything else, or a NULL pointer, is
+ * ZP_ERR_ARG before any device call.  ws: zp_mesh_code_radix_ws_bytes bytes (-1: bad sizes); the
+ * distances of the peel are recomputed per class, so the workspace is O(nv + nf + d^levels). */
+long long zp_mesh_code_radix_ws_bytes(int nv, int nf, int divide, int levels);
+int zp_mesh_code_radix(const float* verts, int nv, const int* faces, int nf, int divide, int levels, int attempts,
+                       int iterations, int grid_log2, long long eps2_q, const uint32_t* draws, int* vertex_ids,
+                       int* face_ids, double* lut, void* ws, void* stream);
 
 /* ---- edge refinement -----------------------------------------------------------------------
  * The refine = True branch of the reference's inference (test.py:276-313): the visible contour of the

@@ -1,4 +1,4 @@
-"""Surface codes of a raw mesh on the device (``zp_mesh_code``, csrc/zp_meshcode.hip).
+"""Surface codes of a raw mesh on the device (``zp_mesh_code`` / ``zp_mesh_code_radix``, csrc/zp_meshcode.hip).
 
 The reference codes a mesh offline with the C++ tool
 Binary_Code_GT_Generator/Generate_Mesh_with_GT_Color (PCL + OpenCV): a recursive balanced 2-means
@@ -8,8 +8,11 @@ outputs are the GT-colour mesh ``models_GT_color/obj_*.ply`` that ``MeshRenderer
 LUT ``Class_CorresPoint*.txt`` that ``Decoder`` reads.  ``encode_mesh`` produces both from a raw
 mesh on the device.  OpenCV's k-means++ draws cannot be reproduced, so the split is restated in
 exact integer arithmetic: the semantics are in include/zp.h (zp_mesh_code) and, as numpy, in
-tests/meshcode_ref.py; results are bit-for-bit reproducible for a given seed.  Binary splits only
-(the reference's ``divide_number`` is fixed at 2).  Dataset walking and OBJ input are out of scope.
+tests/meshcode_ref.py; results are bit-for-bit reproducible for a given seed.  ``encode_mesh`` splits
+in two (the reference's ``divide_number`` 2); ``encode_mesh_radix`` codes a mesh for the d-ary network
+of the code-radix ablation (``divide_number_each_itration`` 4 / 16 / 256) with a balanced d-way split
+per level (zp_mesh_code_radix in include/zp.h, tests/meshcode_radix_ref.py).  Dataset walking and OBJ
+input are out of scope.
 """
 from __future__ import annotations
 
@@ -43,11 +46,14 @@ class MeshCode:
     """Result of ``encode_mesh``: ``vertex_ids`` i32 [nv], ``face_ids`` i32 [nf] and ``lut`` f64
     [2^bits, 3] (NaN rows: classes without a face) as device tensors, ``bits``, the mesh
     (``vertices`` f32 [nv, 3], ``faces`` i32 [nf, 3], numpy) and the ``draws`` u32
-    [attempts, 2^bits - 1] that seeded the split."""
+    [attempts, 2^bits - 1] that seeded the split.  ``divide`` is 2 and ``levels`` is ``bits``.
+    From ``encode_mesh_radix``: ``divide`` = d, ``levels`` = L, ids are the L base-d digits folded MSB
+    first, ``lut`` is [d^L, 3], ``bits`` = L log2 d and ``draws`` is [attempts, (d^L - 1) / (d - 1)]."""
 
-    def __init__(self, vertices, faces, bits, vertex_ids, face_ids, lut, draws):
+    def __init__(self, vertices, faces, bits, vertex_ids, face_ids, lut, draws, divide=2, levels=None):
         self.vertices, self.faces, self.bits = vertices, faces, bits
         self.vertex_ids, self.face_ids, self.lut, self.draws = vertex_ids, face_ids, lut, draws
+        self.divide, self.levels = int(divide), int(bits if levels is None else levels)
 
     def renderer(self, device=None):
         """A ``MeshRenderer`` whose colours carry the face ids (what the label generator draws)."""
@@ -55,17 +61,24 @@ class MeshCode:
                                            device=self.face_ids.device if device is None else device)
 
     def decoder(self, ignore_bit=0, device=None):
+        """The ``Decoder`` of this code's LUT (``class_base=divide`` for a d-ary code, which has no
+        ``ignore_bit``)."""
         from .decode import Decoder
+        if self.divide != 2:
+            if ignore_bit:
+                raise ValueError("ignore_bit needs a binary code (encode_mesh)")
+            return Decoder([self.lut.cpu().numpy()], device=self.lut.device if device is None else device,
+                           class_base=self.divide)
         return Decoder([self.lut.cpu().numpy()], device=self.lut.device if device is None else device,
                        ignore_bit=ignore_bit)
 
     def write_lut_file(self, path):
         """The generator's ``Class_CorresPoint*.txt`` (Generate_Mesh_with_GT_Color.cpp:616-624):
-        ``"N 2 L"``, then ``"id x y z"`` per class with ``%g`` numbers as the C++ stream prints them;
-        a class without a face is written as ``nan``."""
+        ``"N d L"`` (d = 2 and L = bits for the binary code), then ``"id x y z"`` per class with ``%g``
+        numbers as the C++ stream prints them; a class without a face is written as ``nan``."""
         lut = self.lut.cpu().numpy()
         with open(path, "w") as f:
-            f.write(f"{len(lut)} 2 {self.bits}\n")
+            f.write(f"{len(lut)} {self.divide} {self.levels}\n")
             for i, (x, y, z) in enumerate(lut):
                 f.write("%d %s %s %s\n" % (i, *("nan" if v != v else "%g" % v for v in (x, y, z))))
 
@@ -102,6 +115,61 @@ class MeshCode:
             f.write(fo.tobytes())
 
 
+def _check_mesh(vertices, faces, classes, what):
+    """The input checks both coders share -> (vertices f32 [nv, 3], faces i32 [nf, 3]), contiguous."""
+    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float32).reshape(-1, 3))
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] != 3 or not np.issubdtype(f.dtype, np.integer) or len(f) == 0:
+        raise ValueError("faces must be a non-empty integer array [nf, 3]")
+    if len(v) < classes:
+        raise ValueError(f"{len(v)} vertices cannot fill {what} classes")
+    if not np.isfinite(v).all():
+        raise ValueError("non-finite vertex")
+    if f.min() < 0 or f.max() >= len(v):
+        raise ValueError("face index outside the vertex array")
+    return v, np.ascontiguousarray(f.astype(np.int32))
+
+
+def encode_mesh_radix(vertices, faces, divide, levels, attempts=3, iterations=10, eps=1.0, seed=0, device="cuda"):
+    """Code a triangle mesh for the d-ary network: ``levels`` levels of the balanced ``divide``-way
+    split (d a power of two in 4..256, d^levels <= 65536; zp_mesh_code_radix in include/zp.h), with
+    ``attempts`` tries of up to ``iterations`` Lloyd steps per group as in ``encode_mesh``.  vertices
+    [nv, 3] (stored as f32, finite, d^levels <= nv <= 2^21), faces int [nf, 3].  The seeds are sampled on
+    the host from ``numpy.random.default_rng(seed)``.  Returns a ``MeshCode`` whose ids fold the digits
+    as ``Decoder(class_base=divide)`` and the GT digit planes do."""
+    import torch
+    from . import _lib as L
+    d, levels, attempts, iterations = int(divide), int(levels), int(attempts), int(iterations)
+    if d == 2:
+        raise ValueError("divide 2 is the binary code: use encode_mesh")
+    if d < 4 or d > 256 or d & (d - 1):
+        raise ValueError("divide must be a power of two in 4..256")
+    if levels < 1 or d ** levels > 65536:
+        raise ValueError("levels must be >= 1 with divide^levels <= 65536")
+    if attempts < 1 or iterations < 1:
+        raise ValueError("attempts and iterations must be >= 1")
+    C = d ** levels
+    v, f = _check_mesh(vertices, faces, C, f"{d}^{levels}")
+    k = grid_log2(v)
+    eps2 = eps_to_grid(eps, k)
+    draws = np.random.default_rng(seed).integers(0, 1 << 32, size=(attempts, (C - 1) // (d - 1)), dtype=np.uint32)
+    need = L.lib.zp_mesh_code_radix_ws_bytes(len(v), len(f), d, levels)
+    if need < 0:
+        raise ValueError(f"mesh sizes out of range: {len(v)} vertices, {len(f)} faces, {d}^{levels} classes")
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        vd, fd = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
+        dd = torch.from_numpy(draws.view(np.int32)).to(dev)
+        vid = torch.empty(len(v), dtype=torch.int32, device=dev)
+        fid = torch.empty(len(f), dtype=torch.int32, device=dev)
+        lut = torch.empty((C, 3), dtype=torch.float64, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        L.call("zp_mesh_code_radix", vd.data_ptr(), len(v), fd.data_ptr(), len(f), d, levels, attempts, iterations, k,
+               eps2, dd.data_ptr(), vid.data_ptr(), fid.data_ptr(), lut.data_ptr(), ws.data_ptr(), L.stream_ptr(dev))
+        # as in encode_mesh: everything was allocated on this stream, frees are ordered behind the call
+    return MeshCode(v, f, (d.bit_length() - 1) * levels, vid, fid, lut, draws, divide=d, levels=levels)
+
+
 def encode_mesh(vertices, faces, bits=16, attempts=3, iterations=10, eps=1.0, seed=0, device="cuda"):
     """Code a triangle mesh: ``bits`` levels (1..16) of the balanced 2-means split, ``attempts`` tries
     of up to ``iterations`` Lloyd steps per group stopping at a centre shift of ``eps`` mesh units
@@ -111,22 +179,12 @@ def encode_mesh(vertices, faces, bits=16, attempts=3, iterations=10, eps=1.0, se
     Returns a ``MeshCode``."""
     import torch
     from . import _lib as L
-    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float32).reshape(-1, 3))
-    f = np.asarray(faces)
-    if f.ndim != 2 or f.shape[1] != 3 or not np.issubdtype(f.dtype, np.integer) or len(f) == 0:
-        raise ValueError("faces must be a non-empty integer array [nf, 3]")
     bits, attempts, iterations = int(bits), int(attempts), int(iterations)
     if not 1 <= bits <= 16:
         raise ValueError("bits must be in 1..16")
-    if len(v) < 1 << bits:
-        raise ValueError(f"{len(v)} vertices cannot fill 2^{bits} classes")
     if attempts < 1 or iterations < 1:
         raise ValueError("attempts and iterations must be >= 1")
-    if not np.isfinite(v).all():
-        raise ValueError("non-finite vertex")
-    if f.min() < 0 or f.max() >= len(v):
-        raise ValueError("face index outside the vertex array")
-    f = np.ascontiguousarray(f.astype(np.int32))
+    v, f = _check_mesh(vertices, faces, 1 << bits, f"2^{bits}")
     k = grid_log2(v)
     eps2 = eps_to_grid(eps, k)
     draws = np.random.default_rng(seed).integers(0, 1 << 32, size=(attempts, (1 << bits) - 1), dtype=np.uint32)
