@@ -28,6 +28,7 @@
  *   zp_threshold       common_ops.py:5-19 (sigmoid > 0.5 -> {0,1})
  *   zp_decode          binary_code_helper/CNN_output_to_pose.py:34-64, 100-130 and
  *                      class_id_encoder_decoder.py:17-28 (bits -> id -> LUT -> 2D/3D)
+ *   zp_decode_unique   binary_code_helper/CNN_output_to_pose.py:67-91 (one 2D-3D pair per class id)
  *   zp_lut_coarsen     binary_code_helper/generate_new_dict.py:4-33 (ignore_bit LUT)
  *   zp_ce_loss, zp_code_digits, zp_decode_radix, zp_pack_digits
  *                      the d-ary code ablation (config_ablation/exp_lmo_ablation_*: 'CE' loss,
@@ -474,6 +475,23 @@ int zp_code_digits(const float* code_logits, int B, int L, int d, int H, int W, 
 int zp_decode_radix(const float* mask_logits, const float* code_logits, int B, int H, int W, int L, int d,
                     const float* lut, const int* lut_index, const int* bbox, int bbox_size, int* ids,
                     int* counts, int* xy, float* xyz, void* ws, void* stream);
+/* Unique correspondences (build_unique_2D_3D_correspondence, CNN_output_to_pose.py:67-91): one row
+ * per distinct class id under crop b's mask, in the row-major order of each class's first pixel.
+ *   d == 2: bit logits as zp_decode (Lfull channels, the top L used); d > 2: L steps of d class
+ *   logits as zp_decode_radix (Lfull == L * d); at most 2^24 class ids either way.
+ *   mean = (sum x / n, sum y / n) over the class's pixels: exact integer sums, one correctly
+ *   rounded f64 division per axis; xy = (int)(bbox[2]/bbox_size * mean_x + bbox[0]), likewise y
+ *   (f64 multiply, then add, truncation toward zero); xyz = lut[id] or 0 if any component is NaN.
+ *   counts[b] = number of distinct ids; rows at or past counts[b] are unspecified.  Optional:
+ *   ids [B][H][W], mult int32 [B][H*W] (pixels per row), mean_xy f64 [B][H*W][2] (crop-space mean).
+ *   H * W * max(H, W) < 2^31 (the int32 coordinate sums); B <= 65535.
+ *   ws: zp_decode_unique_ws_bytes(B, H, W) bytes (< 48 per pixel plus the tile counts, whatever the
+ *   number of classes), filled on `stream` inside the call.  Results are bitwise reproducible. */
+long long zp_decode_unique_ws_bytes(int B, int H, int W);
+int zp_decode_unique(const float* mask_logits, const float* code_logits, int B, int H, int W, int Lfull,
+                     int L, int d, const float* lut, const int* lut_index, const int* bbox, int bbox_size,
+                     int* ids, int* counts, int* xy, float* xyz, int* mult, double* mean_xy, void* ws,
+                     void* stream);
 /* out[n][3] (f32) = mean over the 2^(old-new) children of lut64 (f64, summed in order) */
 int zp_lut_coarsen(const double* lut64, int old_bits, int new_bits, float* out, void* stream);
 

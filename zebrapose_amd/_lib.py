@@ -118,6 +118,8 @@ _SIGS = {
     "zp_decode": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     "zp_code_digits": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "zp_decode_radix": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "zp_decode_unique_ws_bytes": (i64, [i32, i32, i32]),
+    "zp_decode_unique": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "zp_lut_coarsen": (i32, [vp, i32, i32, vp, vp]),
     "zp_adam": (i32, [vp, vp, vp, vp, i64, f64, f64, f64, f64, i64, vp]),
     "zp_pack_weight_multi": (i32, [i32, vp, vp, i64, vp]),

@@ -98,10 +98,32 @@ def _digits_to_logits(digits, d):
     return out.reshape(L * d, H, W)
 
 
+def build_unique_2D_3D_correspondence(Pixel_position, class_id_image, dict_class_id_3D_points):
+    """:67-91 on host arrays, for scripts that call it directly: one correspondence per class id, in
+    the order the ids first appear among the pixels; Points_2D (f64 [n, 2]) is the mean (x, y) of
+    the id's pixels -- an exact integer sum and one division -- and Points_3D (f64 [n, 3]) the
+    dictionary's rows, NaN rows included, as in the reference.  Pixel_position: (rows, cols), e.g.
+    ``mask.nonzero()``.  The batched device form is ``Decoder(..., unique=True)`` (zp_decode_unique)."""
+    ys = np.asarray(Pixel_position[0]).reshape(-1)
+    xs = np.asarray(Pixel_position[1]).reshape(-1)
+    keys = np.asarray(class_id_image)[ys, xs]
+    uniq, first, inv, cnt = np.unique(keys, return_index=True, return_inverse=True, return_counts=True)
+    order = np.argsort(first, kind="stable")
+    inv = inv.reshape(-1)
+    sx = np.bincount(inv, weights=xs.astype(np.float64), minlength=len(uniq))
+    sy = np.bincount(inv, weights=ys.astype(np.float64), minlength=len(uniq))
+    Points_2D = (np.stack([sx, sy], 1) / cnt[:, None].astype(np.float64))[order].reshape(-1, 2)
+    Points_3D = np.zeros((len(uniq), 3))
+    for i, k in enumerate(uniq[order]):
+        Points_3D[i] = dict_class_id_3D_points[k]
+    return Points_2D, Points_3D
+
+
 def decode_correspondences(mask_image, class_code_image, Bbox, Bbox_Size, dict_class_id_3D_points, device="cuda",
-                           class_base=2):
+                           class_base=2, unique=False):
     """Device version of :110-129 for one crop: (Original_Points_2D int64 [N,2], Points_3D f32 [N,3]).
-    class_base d != 2: class_code_image holds the d-ary digits [H, W, L] (zp_decode_radix)."""
+    class_base d != 2: class_code_image holds the d-ary digits [H, W, L] (zp_decode_radix).
+    unique: :67-91 instead of :53-64, one correspondence per class id (zp_decode_unique)."""
     L = class_code_image.shape[2]
     dec = _decoder_for(dict_class_id_3D_points, device, class_base)
     if class_base != 2:
@@ -109,20 +131,21 @@ def decode_correspondences(mask_image, class_code_image, Bbox, Bbox_Size, dict_c
             raise ValueError(f"code image has {L} digits but the dictionary has {dec.steps} base-{class_base}")
         m = torch.from_numpy(_bits_to_logits(mask_image)[None, None]).to(device)
         c = torch.from_numpy(_digits_to_logits(class_code_image, int(class_base))[None]).to(device)
-        counts, xy, xyz = dec(m, c, np.asarray(Bbox).reshape(1, 4), bbox_size=Bbox_Size)
+        counts, xy, xyz = dec(m, c, np.asarray(Bbox).reshape(1, 4), bbox_size=Bbox_Size, unique=unique)
         return Decoder.to_host(counts, xy, xyz)[0]
     if dec.bits != L:
         raise ValueError(f"code image has {L} bits but the dictionary has {dec.bits}")
     m = torch.from_numpy(_bits_to_logits(mask_image)[None, None]).to(device)
     c = torch.from_numpy(np.ascontiguousarray(_bits_to_logits(class_code_image).transpose(2, 0, 1))[None]).to(device)
-    counts, xy, xyz = dec(m, c, np.asarray(Bbox).reshape(1, 4), bbox_size=Bbox_Size)
+    counts, xy, xyz = dec(m, c, np.asarray(Bbox).reshape(1, 4), bbox_size=Bbox_Size, unique=unique)
     return Decoder.to_host(counts, xy, xyz)[0]
 
 
 def CNN_outputs_to_object_pose(mask_image, class_code_image, Bbox, Bbox_Size, class_base=2,
-                               dict_class_id_3D_points=None, intrinsic_matrix=None):
+                               dict_class_id_3D_points=None, intrinsic_matrix=None, unique=False):
     """:100-160 -- correspondences on the device, then RANSAC-EPnP (cv2) / Progressive-X as in the
-    reference.  Returns (R, t, success)."""
+    reference.  Returns (R, t, success).  unique: the reference's other correspondence builder
+    (:67-91, the switch at :114); success then needs 6 distinct class ids."""
     if intrinsic_matrix is None:
         intrinsic_matrix = np.zeros((3, 3))
         intrinsic_matrix[0, 0] = 572.4114
@@ -132,7 +155,7 @@ def CNN_outputs_to_object_pose(mask_image, class_code_image, Bbox, Bbox_Size, cl
         intrinsic_matrix[2, 2] = 1.0
     success, rot, tvecs = False, [], []
     p2d, p3d = decode_correspondences(mask_image, class_code_image, Bbox, Bbox_Size, dict_class_id_3D_points,
-                                      class_base=class_base)
+                                      class_base=class_base, unique=unique)
     if len(p2d) >= 6:
         success = True
         coord_2d = np.ascontiguousarray(p2d.astype(np.float32))

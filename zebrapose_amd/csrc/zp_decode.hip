@@ -6,6 +6,8 @@
 //   class_id_encoder_decoder.py:17-28                id = sum_i bit_i * 2^(L-1-i)  (channel 0 = MSB)
 //   CNN_output_to_pose.py:53-64                      P2D = (x, y) of mask.nonzero() (row-major),
 //                                                    P3D = LUT[id], NaN rows -> [0,0,0] (kept)
+//   CNN_output_to_pose.py:67-91                      unique form: one row per class id in first-pixel
+//                                                    order, P2D = f64 mean of the class's pixels
 //   CNN_output_to_pose.py:34-50                      x' = int(Bbox[2]/Bbox_Size * x + Bbox[0]) (f64, trunc)
 //   CNN_output_to_pose.py:128-129                    P2D/P3D cast to float32 for PnP
 //   generate_new_dict.py:4-33                        ignore_bit LUT = f64 mean of the 2^k children
@@ -202,6 +204,156 @@ __global__ void __launch_bounds__(256) k_decode_ids_radix(const float* __restric
   if (threadIdx.x == 0) tile_cnt[b * tiles + tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
+// ---- unique correspondences (CNN_output_to_pose.py:67-91): one row per decoded class ----------
+// Per crop an open-addressed table of T = 2^logT >= 2 * HW slots (keys: class id, -1 = empty;
+// first: lowest pixel index of the class, as unsigned, 0xFFFFFFFF = none) and three integer
+// accumulators per pixel (n, sum x, sum y), used at the class's first pixel.  Everything that
+// depends on arrival order is an integer min or sum, so the result does not.
+
+__device__ __forceinline__ uint32_t uq_hash(int id, int logT) { return ((uint32_t)id * 2654435761u) >> (32 - logT); }
+
+// pass 0: keys / first <- all ones (empty, no pixel), the accumulators behind them <- 0
+__global__ void __launch_bounds__(256) k_unique_init(int* __restrict__ tab, size_t n_ones, size_t n_all) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_all; i += (size_t)gridDim.x * 256) tab[i] = i < n_ones ? -1 : 0;
+}
+
+// pass 1: claim the class's slot, lower its first pixel; packed[p] <- slot (or stays -1)
+__global__ void __launch_bounds__(256) k_unique_insert(int* __restrict__ packed, int HW, int logT, int* __restrict__ keys,
+                                                       unsigned* __restrict__ first) {
+  const int b = blockIdx.y;
+  const uint32_t T = 1u << logT;
+  int* kb = keys + ((size_t)b << logT);
+  unsigned* fb = first + ((size_t)b << logT);
+  const int p0 = blockIdx.x * DEC_TILE + threadIdx.x * 4;
+  for (int k = 0; k < 4; ++k) {
+    const int p = p0 + k;
+    if (p >= HW) break;
+    const int v = packed[(size_t)b * HW + p];
+    if (v < 0) continue;
+    uint32_t h = uq_hash(v, logT);
+    int slot = -1;
+    for (uint32_t i = 0; i < T; ++i) {  // at most HW < T keys per crop: an empty slot is always met
+      const int prev = atomicCAS(&kb[h], -1, v);
+      if (prev == -1 || prev == v) {
+        slot = (int)h;
+        break;
+      }
+      h = (h + 1) & (T - 1);
+    }
+    if (slot >= 0) atomicMin(&fb[slot], (unsigned)p);
+    packed[(size_t)b * HW + p] = slot;
+  }
+}
+
+// pass 2: add every pixel into the accumulators of its class's first pixel; count the heads per tile
+__global__ void __launch_bounds__(256) k_unique_accum(const int* __restrict__ slots, int HW, int W, int logT,
+                                                      const unsigned* __restrict__ first, int* __restrict__ acc_n,
+                                                      int* __restrict__ acc_x, int* __restrict__ acc_y,
+                                                      int* __restrict__ head_cnt, int tiles) {
+  const int b = blockIdx.y, tile = blockIdx.x;
+  const unsigned* fb = first + ((size_t)b << logT);
+  const int p0 = tile * DEC_TILE + threadIdx.x * 4;
+  __shared__ int wsum[4];
+  int cnt = 0;
+  for (int k = 0; k < 4; ++k) {
+    const int p = p0 + k;
+    if (p >= HW) break;
+    const int s = slots[(size_t)b * HW + p];
+    if (s < 0) continue;
+    const int f = (int)fb[s];  // <= p: this pixel lowered it in pass 1
+    if ((unsigned)f >= (unsigned)HW) continue;
+    const int py = p / W, px = p - py * W;
+    const size_t o = (size_t)b * HW + f;
+    atomicAdd(&acc_n[o], 1);
+    atomicAdd(&acc_x[o], px);
+    atomicAdd(&acc_y[o], py);
+    cnt += f == p;
+  }
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) head_cnt[b * tiles + tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// pass 3: k_decode_emit over the heads (a pixel that is its class's first), in row-major order
+__global__ void __launch_bounds__(256) k_unique_emit(const int* __restrict__ slots, const int* __restrict__ head_cnt,
+                                                     int tiles, int H, int W, int logT, const int* __restrict__ keys,
+                                                     const unsigned* __restrict__ first, const int* __restrict__ acc_n,
+                                                     const int* __restrict__ acc_x, const int* __restrict__ acc_y,
+                                                     size_t lut_floats, const float* __restrict__ lut,
+                                                     const int* __restrict__ lut_index, const int* __restrict__ bbox,
+                                                     int bbox_size, int* __restrict__ counts, int* __restrict__ xy,
+                                                     float* __restrict__ xyz, int* __restrict__ mult,
+                                                     double* __restrict__ mean_xy) {
+  // every f64 operation of this kernel is rounded on its own.  The __dmul_rn / __dadd_rn wrappers do
+  // not ensure that: they inline to a plain multiply and add, which the compiler contracts into an FMA.
+#pragma clang fp contract(off)
+  const int b = blockIdx.y, tile = blockIdx.x;
+  const int HW = H * W;
+  __shared__ int scan[256];
+  __shared__ int base_s;
+  if (threadIdx.x == 0) {
+    int base = 0, total = 0;
+    for (int t = 0; t < tiles; ++t) {
+      int c = head_cnt[b * tiles + t];
+      if (t < tile) base += c;
+      total += c;
+    }
+    base_s = base;
+    if (tile == 0) counts[b] = total;
+  }
+  const int* kb = keys + ((size_t)b << logT);
+  const unsigned* fb = first + ((size_t)b << logT);
+  const int p0 = tile * DEC_TILE + threadIdx.x * 4;
+  int v[4];
+  int mine = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int p = p0 + k;
+    const int s = p < HW ? slots[(size_t)b * HW + p] : -1;
+    v[k] = (s >= 0 && (int)fb[s] == p) ? kb[s] : -1;
+    mine += v[k] >= 0;
+  }
+  scan[threadIdx.x] = mine;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {
+    int t = threadIdx.x >= off ? scan[threadIdx.x - off] : 0;
+    __syncthreads();
+    scan[threadIdx.x] += t;
+    __syncthreads();
+  }
+  int pos = base_s + scan[threadIdx.x] - mine;
+  const double bx = bbox[b * 4 + 0], by = bbox[b * 4 + 1];
+  const double rx = (double)bbox[b * 4 + 2] / (double)bbox_size;
+  const double ry = (double)bbox[b * 4 + 3] / (double)bbox_size;
+  const float* L3 = lut + (size_t)(lut_index ? lut_index[b] : 0) * lut_floats;
+  int* oxy = xy + (size_t)b * HW * 2;
+  float* oxyz = xyz + (size_t)b * HW * 3;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (v[k] < 0) continue;
+    const size_t o = (size_t)b * HW + p0 + k;
+    const int n = acc_n[o];
+    // exact integer sums, one correctly rounded division per axis; then multiply, add (no FMA), truncate
+    const double mx = (double)acc_x[o] / (double)n;
+    const double my = (double)acc_y[o] / (double)n;
+    const double tx = rx * mx, ty = ry * my;
+    oxy[2 * pos] = (int)(tx + bx);
+    oxy[2 * pos + 1] = (int)(ty + by);
+    float a = L3[(size_t)v[k] * 3], c = L3[(size_t)v[k] * 3 + 1], d = L3[(size_t)v[k] * 3 + 2];
+    if (isnan(a) || isnan(c) || isnan(d)) a = c = d = 0.f;
+    oxyz[3 * pos] = a;
+    oxyz[3 * pos + 1] = c;
+    oxyz[3 * pos + 2] = d;
+    if (mult) mult[(size_t)b * HW + pos] = n;
+    if (mean_xy) {
+      mean_xy[((size_t)b * HW + pos) * 2] = mx;
+      mean_xy[((size_t)b * HW + pos) * 2 + 1] = my;
+    }
+    ++pos;
+  }
+}
+
 __global__ void k_lut_coarsen(const double* __restrict__ lut, int k, int n_new, float* __restrict__ out) {
   int nid = blockIdx.x * blockDim.x + threadIdx.x;
   if (nid >= n_new) return;
@@ -279,6 +431,71 @@ extern "C" int zp_decode_radix(const float* mask_logits, const float* code_logit
   hipLaunchKernelGGL(k_decode_emit, dim3(tiles, B), dim3(256), 0, st, packed, tile_cnt, tiles, H, W, (size_t)3 * nid, lut,
                      lut_index, bbox, bbox_size, counts, xy, xyz);
   ZP_LAUNCH_CHECK("zp_decode_radix emit");
+  return ZP_OK;
+}
+
+// workspace of zp_decode_unique: slots [B][HW], mask and head tile counts [2][B][tiles], then
+// keys [B][T] and first [B][T] (filled with ones), then n / sum x / sum y [3][B][HW] (zeroed): k_unique_init
+static int uq_log_table(long long HW) {
+  int logT = 1;
+  while ((1ll << logT) < 2 * HW) ++logT;
+  return logT;
+}
+
+extern "C" long long zp_decode_unique_ws_bytes(int B, int H, int W) {
+  long long HW = (long long)H * W;
+  long long tiles = (HW + DEC_TILE - 1) / DEC_TILE;
+  long long T = 1ll << uq_log_table(HW);
+  return (long long)B * HW * 4 + 2 * (long long)B * tiles * 4 + 2 * (long long)B * T * 4 + 3 * (long long)B * HW * 4 + 256;
+}
+
+extern "C" int zp_decode_unique(const float* mask_logits, const float* code_logits, int B, int H, int W, int Lfull, int L,
+                                int d, const float* lut, const int* lut_index, const int* bbox, int bbox_size, int* ids,
+                                int* counts, int* xy, float* xyz, int* mult, double* mean_xy, void* ws, void* stream) {
+  ZP_CHECK_ARG(mask_logits && code_logits && lut && bbox && counts && xy && xyz && ws, "zp_decode_unique: null pointer");
+  ZP_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && L >= 1 && d >= 2 && d <= 256 && bbox_size > 0,
+               "zp_decode_unique: bad sizes");
+  long long nid = 1;  // class ids: 2^L (d == 2) or d^L, at most 2^24 as in zp_decode / zp_decode_radix
+  for (int i = 0; i < L && nid <= (1ll << 24); ++i) nid *= d;
+  ZP_CHECK_ARG(nid <= (1ll << 24), "zp_decode_unique: %d steps of %d classes exceed 2^24 class ids", L, d);
+  ZP_CHECK_ARG(d == 2 ? L <= Lfull : Lfull == L * d, "zp_decode_unique: %d code channels for %d steps of %d classes", Lfull,
+               L, d);
+  // a class may hold every pixel: its coordinate sums stay below HW * max(H, W), kept in int32
+  ZP_CHECK_ARG((long long)H * W * (H > W ? H : W) < (1ll << 31),
+               "zp_decode_unique: %d x %d crops could overflow the int32 coordinate sums", H, W);
+  const int HW = H * W;
+  const int tiles = (HW + DEC_TILE - 1) / DEC_TILE;
+  const int logT = uq_log_table(HW);
+  const size_t T = (size_t)1 << logT;
+  int* slots = (int*)ws;
+  int* tile_cnt = slots + (size_t)B * HW;
+  int* head_cnt = tile_cnt + (size_t)B * tiles;
+  int* keys = head_cnt + (size_t)B * tiles;
+  unsigned* first = (unsigned*)(keys + (size_t)B * T);
+  int* acc_n = (int*)(first + (size_t)B * T);
+  int* acc_x = acc_n + (size_t)B * HW;
+  int* acc_y = acc_x + (size_t)B * HW;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n_ones = 2 * (size_t)B * T, n_all = n_ones + 3 * (size_t)B * HW;  // keys, first | n, sum x, sum y
+  const size_t init_blocks = (n_all + 255) / 256;
+  hipLaunchKernelGGL(k_unique_init, dim3((unsigned)(init_blocks < 4096 ? init_blocks : 4096)), dim3(256), 0, st, keys, n_ones,
+                     n_all);
+  ZP_LAUNCH_CHECK("zp_decode_unique init");
+  if (d == 2)
+    hipLaunchKernelGGL(k_decode_ids, dim3(tiles, B), dim3(256), 0, st, mask_logits, code_logits, HW, Lfull, L, slots, ids,
+                       tile_cnt, tiles);
+  else
+    hipLaunchKernelGGL(k_decode_ids_radix, dim3(tiles, B), dim3(256), 0, st, mask_logits, code_logits, HW, L, d, slots,
+                       ids, tile_cnt, tiles);
+  ZP_LAUNCH_CHECK("zp_decode_unique ids");
+  hipLaunchKernelGGL(k_unique_insert, dim3(tiles, B), dim3(256), 0, st, slots, HW, logT, keys, first);
+  ZP_LAUNCH_CHECK("zp_decode_unique insert");
+  hipLaunchKernelGGL(k_unique_accum, dim3(tiles, B), dim3(256), 0, st, slots, HW, W, logT, first, acc_n, acc_x, acc_y,
+                     head_cnt, tiles);
+  ZP_LAUNCH_CHECK("zp_decode_unique accum");
+  hipLaunchKernelGGL(k_unique_emit, dim3(tiles, B), dim3(256), 0, st, slots, head_cnt, tiles, H, W, logT, keys, first,
+                     acc_n, acc_x, acc_y, (size_t)3 * nid, lut, lut_index, bbox, bbox_size, counts, xy, xyz, mult, mean_xy);
+  ZP_LAUNCH_CHECK("zp_decode_unique emit");
   return ZP_OK;
 }
 

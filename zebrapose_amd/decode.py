@@ -8,15 +8,22 @@ correspondences without leaving the GPU:
     xy[b, :counts[b]]  original-image pixel (x, y), int32, row-major mask order
     xyz[b, :counts[b]] LUT vertex (f32), [0, 0, 0] for empty (NaN) classes
 
-Reference: binary_code_helper/CNN_output_to_pose.py:10-64, 100-130,
+``unique=True`` / ``Decoder.unique`` give the reference's other form (``zp_decode_unique``): one row
+per distinct class id under the mask, at the mean position of the class's pixels.
+
+Reference: binary_code_helper/CNN_output_to_pose.py:10-91, 100-130,
 class_id_encoder_decoder.py:17-28, generate_new_dict.py:4-33, common_ops.py:5-19.
 """
 from __future__ import annotations
+
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 from . import _lib as L
+
+UniqueCorrespondences = namedtuple("UniqueCorrespondences", "counts xy xyz mult mean_xy ids")
 
 
 def read_lut_file(path):
@@ -76,7 +83,33 @@ class Decoder:
         self.lut = torch.stack(tabs).contiguous()
         self.device = torch.device(device)
 
-    def __call__(self, mask_logits, code_logits, bboxes, bbox_size=128, lut_index=None, return_ids=False):
+    def __call__(self, mask_logits, code_logits, bboxes, bbox_size=128, lut_index=None, return_ids=False,
+                 unique=False):
+        """unique=True: one correspondence per decoded class id instead of one per mask pixel
+        (``unique``, same return shape: it drops into ``PnP()``)."""
+        if unique:
+            u = self._unique(mask_logits, code_logits, bboxes, bbox_size, lut_index, return_ids, False)
+            return (u.counts, u.xy, u.xyz, u.ids) if return_ids else (u.counts, u.xy, u.xyz)
+        mask_logits, code_logits, B, H, W, Lfull, bb, li = self._inputs(mask_logits, code_logits, bboxes, lut_index)
+        dev = mask_logits.device
+        counts = torch.empty(B, dtype=torch.int32, device=dev)
+        xy = torch.empty((B, H * W, 2), dtype=torch.int32, device=dev)
+        xyz = torch.empty((B, H * W, 3), dtype=torch.float32, device=dev)
+        ids = torch.empty((B, H, W), dtype=torch.int32, device=dev) if return_ids else None
+        ws = torch.empty(int(L.lib.zp_decode_ws_bytes(B, H, W)), dtype=torch.uint8, device=dev)
+        if self.class_base != 2:
+            L.call("zp_decode_radix", mask_logits.data_ptr(), code_logits.data_ptr(), B, H, W, self.steps,
+                   self.class_base, self.lut.data_ptr(), L.ptr(li), bb.data_ptr(), int(bbox_size), L.ptr(ids),
+                   counts.data_ptr(), xy.data_ptr(), xyz.data_ptr(), ws.data_ptr(), L.stream_ptr())
+        else:
+            L.call("zp_decode", mask_logits.data_ptr(), code_logits.data_ptr(), B, H, W, Lfull, self.bits,
+                   self.lut.data_ptr(), L.ptr(li), bb.data_ptr(), int(bbox_size), L.ptr(ids), counts.data_ptr(),
+                   xy.data_ptr(), xyz.data_ptr(), ws.data_ptr(), L.stream_ptr())
+        if return_ids:
+            return counts, xy, xyz, ids
+        return counts, xy, xyz
+
+    def _inputs(self, mask_logits, code_logits, bboxes, lut_index):
         mask_logits = mask_logits.detach().contiguous().float()
         code_logits = code_logits.detach().contiguous().float()
         B, _, H, W = mask_logits.shape
@@ -94,22 +127,33 @@ class Decoder:
         li = None
         if lut_index is not None:
             li = torch.as_tensor(np.asarray(lut_index), dtype=torch.int32).reshape(B).to(dev).contiguous()
+        return mask_logits, code_logits, B, H, W, Lfull, bb, li
+
+    def unique(self, mask_logits, code_logits, bboxes, bbox_size=128, lut_index=None):
+        """Unique 2D-3D correspondences (CNN_output_to_pose.py:67-91, ``zp_decode_unique``): one row
+        per distinct class id under the crop's mask, in the row-major order of each class's first
+        pixel.  -> UniqueCorrespondences(counts [B], xy int32 [B, HW, 2] (the mapped, truncated mean
+        pixel), xyz f32 [B, HW, 3], mult int32 [B, HW] (pixels per row), mean_xy f64 [B, HW, 2]
+        (crop-space mean before the map), ids int32 [B, H, W]); rows at or past counts[b] are
+        unspecified."""
+        return self._unique(mask_logits, code_logits, bboxes, bbox_size, lut_index, True, True)
+
+    def _unique(self, mask_logits, code_logits, bboxes, bbox_size, lut_index, want_ids, want_stats):
+        mask_logits, code_logits, B, H, W, Lfull, bb, li = self._inputs(mask_logits, code_logits, bboxes, lut_index)
+        dev = mask_logits.device
         counts = torch.empty(B, dtype=torch.int32, device=dev)
         xy = torch.empty((B, H * W, 2), dtype=torch.int32, device=dev)
         xyz = torch.empty((B, H * W, 3), dtype=torch.float32, device=dev)
-        ids = torch.empty((B, H, W), dtype=torch.int32, device=dev) if return_ids else None
-        ws = torch.empty(int(L.lib.zp_decode_ws_bytes(B, H, W)), dtype=torch.uint8, device=dev)
-        if self.class_base != 2:
-            L.call("zp_decode_radix", mask_logits.data_ptr(), code_logits.data_ptr(), B, H, W, self.steps,
-                   self.class_base, self.lut.data_ptr(), L.ptr(li), bb.data_ptr(), int(bbox_size), L.ptr(ids),
-                   counts.data_ptr(), xy.data_ptr(), xyz.data_ptr(), ws.data_ptr(), L.stream_ptr())
-        else:
-            L.call("zp_decode", mask_logits.data_ptr(), code_logits.data_ptr(), B, H, W, Lfull, self.bits,
-                   self.lut.data_ptr(), L.ptr(li), bb.data_ptr(), int(bbox_size), L.ptr(ids), counts.data_ptr(),
-                   xy.data_ptr(), xyz.data_ptr(), ws.data_ptr(), L.stream_ptr())
-        if return_ids:
-            return counts, xy, xyz, ids
-        return counts, xy, xyz
+        ids = torch.empty((B, H, W), dtype=torch.int32, device=dev) if want_ids else None
+        mult = torch.empty((B, H * W), dtype=torch.int32, device=dev) if want_stats else None
+        mean_xy = torch.empty((B, H * W, 2), dtype=torch.float64, device=dev) if want_stats else None
+        ws = torch.empty(int(L.lib.zp_decode_unique_ws_bytes(B, H, W)), dtype=torch.uint8, device=dev)
+        steps = self.steps if self.class_base != 2 else self.bits
+        L.call("zp_decode_unique", mask_logits.data_ptr(), code_logits.data_ptr(), B, H, W, Lfull, steps,
+               self.class_base, self.lut.data_ptr(), L.ptr(li), bb.data_ptr(), int(bbox_size), L.ptr(ids),
+               counts.data_ptr(), xy.data_ptr(), xyz.data_ptr(), L.ptr(mult), L.ptr(mean_xy), ws.data_ptr(),
+               L.stream_ptr())
+        return UniqueCorrespondences(counts, xy, xyz, mult, mean_xy, ids)
 
     @staticmethod
     def to_host(counts, xy, xyz):

@@ -49,13 +49,14 @@ def _state_stamp(ts, engines):
 
 class GraphedInference:
     def __init__(self, net, batch: int, size: int = 256, decoder=None, bbox_size: int = 128, warmup: int = 2,
-                 device=None):
+                 device=None, unique: bool = False):
         if net.training:
             raise ValueError("GraphedInference captures the eval forward: call net.eval() first")
         dev = torch.device(device) if device is not None else next(net.parameters()).device
         if dev.type != "cuda":
             raise ValueError("GraphedInference needs the network on a HIP device")
         self.net, self.decoder, self.bbox_size = net, decoder, int(bbox_size)
+        self.unique = bool(unique)  # the decoder's unique form (one correspondence per class id)
         self.warmup, self.dev = warmup, dev
         self.x = torch.zeros((batch, 3, size, size), dtype=torch.float32, device=dev)
         self.bb = torch.zeros((batch, 4), dtype=torch.int32, device=dev)
@@ -119,7 +120,8 @@ class GraphedInference:
         mask, code = self.net(self.x)
         if self.decoder is None:
             return mask, code
-        counts, xy, xyz = self.decoder(mask, code, self.bb, bbox_size=self.bbox_size)
+        kw = {"unique": True} if self.unique else {}
+        counts, xy, xyz = self.decoder(mask, code, self.bb, bbox_size=self.bbox_size, **kw)
         return mask, code, counts, xy, xyz
 
     def __call__(self, x, bboxes=None):

@@ -22,9 +22,10 @@ from .pnp import PnP
 
 class MultiObjectPose:
     def __init__(self, nets, luts, precision="fp16", bbox_size=128, ignore_bit=0, device="cuda",
-                 pnp=None):
+                 pnp=None, unique=False):
         """nets: one ``BinaryCodeNet_Deeplab`` per object (same code length); luts: the matching
-        [2^L, 3] class-id -> vertex tables (``read_lut_file`` / ``load_dict_class_id_3D_points``)."""
+        [2^L, 3] class-id -> vertex tables (``read_lut_file`` / ``load_dict_class_id_3D_points``);
+        unique: PnP on one correspondence per decoded class id (``Decoder(..., unique=True)``)."""
         if len(nets) != len(luts) or not nets:
             raise ValueError("one LUT per object network")
         self.nets = list(nets)
@@ -35,6 +36,7 @@ class MultiObjectPose:
         self.decoder = Decoder(list(luts), device=device, ignore_bit=ignore_bit)
         self.bbox_size = int(bbox_size)
         self.pnp = pnp or PnP()
+        self.unique = bool(unique)
 
     @torch.no_grad()
     def __call__(self, crops, obj_index, bboxes, K=None):
@@ -68,7 +70,8 @@ class MultiObjectPose:
             K = np.asarray(K, dtype=np.float64)
             if K.ndim == 3:
                 K = K[order]
-        counts, xy, xyz = self.decoder(mask, code, bb, bbox_size=self.bbox_size, lut_index=so.astype(np.int32))
+        counts, xy, xyz = self.decoder(mask, code, bb, bbox_size=self.bbox_size, lut_index=so.astype(np.int32),
+                                      unique=self.unique)
         R, t, ok, inl = self.pnp(counts, xy, xyz, K)
         inv = torch.from_numpy(np.argsort(order, kind="stable")).to(dev)
         out = dict(mask=mask, code=code, counts=counts, xy=xy, xyz=xyz, R=R, t=t, success=ok, inliers=inl)
