@@ -959,6 +959,33 @@ int zp_icp(int B, int N, const double* src_pts, const int* src_counts, int src_c
            double* R_out, double* t_out, int* status, int* iterations, double* mean_error, int* nn, double* T,
            void* ws, void* stream);
 
+/* ---- model info -----------------------------------------------------------------------------
+ * The diameter and the box of one entry of BOP's models_info.json, from the model's points.  The
+ * reference reads them from the file that ships with a dataset (test.py:136, train_v6.py:118); its own
+ * routine for the diameter is lib/pysixd/misc.py:952-966 (calc_pts_diameter), n numpy passes over all
+ * n (n + 1) / 2 pairs.  The semantics are restated here and, in numpy, in tests/modelinfo_ref.py.  Each
+ * f64 operation below is rounded on its own (no fused multiply-add), so the result is defined bit for
+ * bit; nothing depends on how the pairs are split over the device, there are no atomics, and two runs
+ * give the same bits.
+ *
+ * zp_model_info: pts f32 [n][3] (as zp_pose_error takes them) -> out f64 [8], pair i32 [2], status i32 [1].
+ *   d2(i, j), i <= j: dx = f64(x_i) - f64(x_j), likewise dy, dz; d2 = (dx dx + dy dy) + dz dz: what
+ *             (pts_diff * pts_diff).sum(axis=1) gives on the f64 copies BOP's load_ply makes of f32 files.
+ *   out[7]    d2max = the largest d2(i, j) over all i <= j.  The pairs include i = j, as the reference's
+ *             pts[pt_id:] does: one point, or n equal points, give 0.
+ *   out[6]    diameter = sqrt(d2max) as the device's f64 square root gives it.  That it is the correctly
+ *             rounded one is not established here: a caller that needs the bits of the host's
+ *             sqrt(d2max) takes that root itself from out[7] (zebrapose_amd.modelinfo does).
+ *   pair      the lexicographically lowest (i, j), i <= j, with d2(i, j) == d2max; may be NULL.
+ *   out[0..2] min x, y, z: the f32 minimum widened to f64;  out[3..5] size x, y, z = f64(max) - f64(min).
+ *             -0 orders below +0 in both.
+ *   status    0, or 1 when any coordinate is not finite; the other outputs are then unspecified.
+ *   n >= 1 and 3 n < 2^31 - 1024; anything else, or a NULL pts / out / status / ws, is ZP_ERR_ARG before
+ *   any device call.  ws: zp_model_info_ws_bytes(n) bytes (-1: bad n), one 16-byte partial per
+ *   workgroup of a fixed grid: it does not grow with n. */
+long long zp_model_info_ws_bytes(int n);
+int zp_model_info(const float* pts, int n, double* out, int* pair, int* status, void* ws, void* stream);
+
 /* ---- optimizer ----------------------------------------------------------------------- */
 /* torch.optim.Adam (no weight decay, amsgrad off) over one flat f32 buffer; step >= 1 */
 int zp_adam(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n,

@@ -164,6 +164,8 @@ _SIGS = {
     "zp_icp_ws_bytes": (i64, [i32, i32]),
     "zp_icp": (i32, [i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, f64, i32, f64, f64, vp, vp, vp, vp, vp, vp, vp,
                      vp, vp, vp, vp]),
+    "zp_model_info_ws_bytes": (i64, [i32]),
+    "zp_model_info": (i32, [vp, i32, vp, vp, vp, vp, vp]),
 }
 
 

@@ -72,6 +72,12 @@ class MeshCode:
         return Decoder([self.lut.cpu().numpy()], device=self.lut.device if device is None else device,
                        ignore_bit=ignore_bit)
 
+    def model_info(self, **sym):
+        """This mesh's entry of models_info.json (``modelinfo.model_info`` of the vertices, on the
+        code's device); ``symmetries_discrete`` / ``symmetries_continuous`` are passed through."""
+        from .modelinfo import model_info
+        return model_info(self.vertices, device=self.face_ids.device, **sym)
+
     def write_lut_file(self, path):
         """The generator's ``Class_CorresPoint*.txt`` (Generate_Mesh_with_GT_Color.cpp:616-624):
         ``"N d L"`` (d = 2 and L = bits for the binary code), then ``"id x y z"`` per class with ``%g``

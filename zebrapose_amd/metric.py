@@ -10,6 +10,10 @@ forms; ``mssd`` / ``mspd`` / ``vsd`` keep the argument order of lib/pysixd/pose_
 (host arrays in, floats out).  VSD is the 'step' cost under 'bop19' visibility, on depth rendered by
 ``MeshRenderer`` (zp_render), not by OpenGL.  ``symmetry_transformations`` is
 misc.get_symmetry_transformations (misc.py:206-254); ``bop_recall`` averages recalls over thresholds.
+
+``add_scores`` / ``auc_posecnn`` are the tail of test.py (:62-82, :465-483, :515-523) that turns
+per-sample errors and the model's diameter (``modelinfo.model_diameter``) into the paper's numbers:
+the pass rates at 0.1 / 0.05 / 0.02 d and the two AUCs.  They are glue on torch in f64, host or device.
 """
 from __future__ import annotations
 
@@ -249,3 +253,62 @@ def bop_recall(errors, thresholds):
     th = torch.as_tensor(np.asarray(thresholds) if not torch.is_tensor(thresholds) else thresholds,
                          dtype=torch.float64).to(e.device)
     return float((e.unsqueeze(-1) < th).to(torch.float64).mean().item())
+
+
+# ---- the score tail of test.py -------------------------------------------------------------------------
+
+FAILED_ERROR = 10000.0  # test.py:465-469: what a failed PnP or a NaN error counts as (mm)
+
+
+def _errors64(errors):
+    e = torch.as_tensor(errors if torch.is_tensor(errors) else np.asarray(errors))
+    return e.to(torch.float64).reshape(-1)
+
+
+def auc_posecnn(errors_m):
+    """compute_auc_posecnn (test.py:62-82) on errors in metres, host or device: the area under the
+    accuracy-over-threshold curve up to 0.1 m, times 10.  The errors are sorted ascending; entry k
+    (from 1) carries the accuracy k / N, values above 0.1 (and NaN) drop out of the curve but stay in
+    N; the curve is made monotone and integrated over the steps between distinct values, from 0 to 0.1,
+    each step at the accuracy of the first entry at its upper end.  NaN when nothing is <= 0.1."""
+    d, _ = torch.sort(_errors64(errors_m))
+    N = d.numel()
+    keep = d <= 0.1
+    k = int(keep.sum().item())
+    if k == 0:
+        return float("nan")
+    d = d[keep]
+    acc = torch.arange(1, k + 1, dtype=torch.float64, device=d.device) / N
+    edge = torch.tensor([0.0], dtype=torch.float64, device=d.device)
+    rec = torch.cat([edge, d, edge + 0.1])
+    pre = torch.cummax(torch.cat([edge, acc, acc[-1:]]), 0).values
+    step = rec[1:] - rec[:-1]
+    return float((torch.where(step != 0, step * pre[1:], torch.zeros_like(step)).sum() * 10).item())
+
+
+def add_scores(errors, diameter, success=None, fractions=(0.1, 0.05, 0.02)):
+    """The numbers test.py prints from per-sample ADD / ADI errors in millimetres (:465-483, :515-523).
+    ``errors`` [N] host or device; ``success`` bool [N] or None (all succeeded): a failed sample and a
+    NaN error count as 10000.  Returns a dict of floats: ``pass`` (one rate per fraction, strict
+    ``error < diameter * f``), ``auc_steps`` (the mean share of the thresholds 10, 20 .. 100 an error
+    is strictly below), ``auc_posecnn`` (of the errors / 1000) and ``mean_error``."""
+    e = _errors64(errors)
+    if e.numel() == 0:
+        raise ValueError("no errors")
+    bad = e.isnan()
+    if success is not None:
+        s = torch.as_tensor(success if torch.is_tensor(success) else np.asarray(success)).reshape(-1)
+        if s.numel() != e.numel():
+            raise ValueError(f"{s.numel()} success flags for {e.numel()} errors")
+        bad = bad | ~s.to(device=e.device, dtype=torch.bool)
+    e = torch.where(bad, torch.full_like(e, FAILED_ERROR), e)
+    d = float(diameter)
+    th = torch.tensor([d * float(f) for f in fractions], dtype=torch.float64, device=e.device)
+    rates = (e.unsqueeze(-1) < th).to(torch.float64).mean(0)
+    steps = torch.linspace(10, 100, 10, dtype=torch.float64, device=e.device)
+    # the counts are exact; the mean of the shares count / 10 is numpy's, as the reference's is (test.py:519):
+    # a sum of tenths depends on its order, and this one equals np.mean(AUC_ADX_error) bit for bit
+    below = (e.unsqueeze(-1) < steps).sum(-1).to(torch.uint8).cpu().numpy()
+    auc_steps = np.mean(below / 10)
+    return {"pass": [float(r) for r in rates.cpu().tolist()], "auc_steps": float(auc_steps),
+            "auc_posecnn": auc_posecnn(e / 1000.0), "mean_error": float(e.mean().item())}
