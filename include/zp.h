@@ -747,6 +747,81 @@ int zp_render(int B, const float* verts, int nv, const int* faces, int nf, const
               const double* R, const double* t, const double* K, int H, int W, double z_near,
               uint8_t* color, float* depth, uint8_t* mask, int* face_out, void* ws, void* stream);
 
+/* ---- shaded renderer ------------------------------------------------------------------------
+ * zp_render plus a Phong-shaded colour image of a vertex-coloured mesh, replacing the reference's
+ * OpenGL renderer lib/meshrenderer/meshrenderer_phong.py with shader/depth_shader_phong.vs / .frag
+ * (synthetic frames of the train_render kind, the debug renders of test.py:316-327).
+ *   zp_render's inputs, plus vert_normals f32 [nv][3], vert_rgb u8 [nv][3] (red, green, blue) and
+ *   light f64 [B][6] = (lx, ly, lz, ambient, diffuse, specular) (device), the light's position in
+ *   this project's camera coordinates (X right, Y down, Z forward); all three needed only for shaded.
+ *   Outputs (each may be NULL): shaded u8 [B][H][W][3] in B, G, R order as zp_crop_image takes images,
+ *   background 0; color, depth, mask, face_out as zp_render's, from the same visibility pass.
+ * Visibility is zp_render's own device code (snapping, discards, exact int64 coverage, top-left rule,
+ * 64-bit atomic-max key): the four common outputs equal zp_render's bit for bit.
+ * Shading (tests/shade_ref.py restates it in numpy; shaded matches it bit for bit): all f64, every
+ * step one IEEE operation in the order written, only + - * / and sqrt.  unit(v) = v / sqrt((x x +
+ * y y) + z z), and a vector whose length is not > 0 stays zero.
+ *   vertex:   P = (Xc, Yc, Zc) as zp_render's; n_e = unit(((r0 nx + r1 ny) + r2 nz) per row of R);
+ *             L_v = unit(light - P); V_v = -P.
+ *   pixel:    f = the face in the pixel's key; E12, E20, E01 its exact int64 edge values at the
+ *             sample; b_i = f64(E_i) (1/Z_i); q = (b0 + b1) + b2 (the q of the depth rule); every
+ *             attribute a (colour / 255, n_e, L_v, V_v) interpolates as ((b0 a0 + b1 a1) + b2 a2) / q.
+ *   Phong:    N, Ld, Vd = unit of the interpolated n_e, L_v, V_v; nl = (N0 Ld0 + N1 Ld1) + N2 Ld2;
+ *             d = nl > 0 ? nl : 0; Rv = (2 nl) N - Ld; s = max(Rv . Vd, 0) likewise (no shininess
+ *             exponent: the reference has none); per channel o = (ka c + kd (d c)) + ks (s c), clamped
+ *             to <= 1; byte = rint(255 o), half to even (a negative or NaN o gives 0).
+ *   No culling: a back face gets d = 0 and shows its ambient term, as under GL (and whatever specular
+ *   the formula above gives it: as in the reference's shader, s is not gated by d).
+ * Deviations from the reference: its vertex shader normalises the 4-vector transpose(inverse(view)) *
+ * vec4(normal, 1) and takes xyz, which scales the interpolated normal by a per-vertex factor; here
+ * R n is normalised in 3-space.  The light is given in this project's camera frame: gl_utils/camera.py
+ * realCamera builds view = diag(1, 1, -1) [R | t], so GL's eye frame is (Xc, Yc, -Zc) and the
+ * reference's default light (400, 400, 400) is (400, 400, -400) here (zebrapose_amd.render's default).
+ * f64 instead of GL's f32, and zp_render's deviations (no near / far clipping, 1/256 px snapping);
+ * parity with a GL implementation is unpinned, as for zp_render.
+ * Sizes as zp_render.  ws: zp_render_shaded_ws_bytes bytes (-1: bad sizes). */
+long long zp_render_shaded_ws_bytes(int B, int nv, int nf, int H, int W);
+int zp_render_shaded(int B, const float* verts, const float* vert_normals, const uint8_t* vert_rgb, int nv,
+                     const int* faces, int nf, const uint8_t* face_bgr, const double* R, const double* t,
+                     const double* K, const double* light, int H, int W, double z_near, uint8_t* shaded,
+                     uint8_t* color, float* depth, uint8_t* mask, int* face_out, void* ws, void* stream);
+
+/* ---- compositor -----------------------------------------------------------------------------
+ * A rendered object over a background, replacing GDR_Net_Augmentation.py:78-153 (get_bg_image,
+ * replace_bg with resize_short_edge :37-74) with no host round trip.
+ * zp_mask_bbox: mask u8 [B][H][W] -> bbox i32 [B][4] = (r1, c1, r2, c2), the inclusive row / column
+ * bounds of the nonzero pixels; an empty mask gives (0, 0, -1, -1).
+ * zp_composite: fg u8 [B][H][W][3], mask u8 [B][H][W], bbox as above; bgs u8 [n_bg][Hb][Wb][3];
+ * per sample (device arrays) bg_index i32 [B], bg_geo i32 [B][4] = (crop_w, crop_h, out_w, out_h),
+ * bg_f f64 [B] = the factor f that resize_short_edge passes as fx = fy (zebrapose_amd.synth.bg_geometry
+ * computes geo and f), trunc f64 [B][2] = (rnd, u).  Outputs (each may be NULL): out u8 [B][H][W][3],
+ * mask_out u8 [B][H][W] (255 / 0).  tests/synth_ref.py restates both in numpy; the outputs match it
+ * bit for bit.
+ *   truncation (replace_bg:128-149, rows r, columns c; uniform(a, b) = a + (b - a) u in f64, int()
+ *   truncates; mid_r = 0.5 (r1 + r2), mid_c = 0.5 (c1 + c2)):
+ *     rnd < 0 off; rnd < 0.2 clears rows below int(uniform(r1, mid_r)); rnd < 0.4 rows from
+ *     int(uniform(mid_r, r2)) on; rnd < 0.6 columns below int(uniform(c1, mid_c)); rnd < 0.8 columns
+ *     from int(uniform(mid_c, c2)) on; otherwise (a NaN included) nothing.
+ *   pixel: fg where the truncated mask is set, else the background pixel: the top-left crop_w x crop_h
+ *     of bgs[bg_index] resized to out_w x out_h and pasted at the top-left of a zero image.
+ *   resize: cv2.resize(crop, None, fx=f, fy=f, INTER_LINEAR) for u8 as OpenCV 4.x's generic path
+ *     (the arithmetic of oracle/crop_ref.py): the sampling scale is 1 / f (not crop / out); source
+ *     position f32((i + 1/2) scale - 1/2), floor and fraction in f32, clamped to the first / last
+ *     sample; weights rint(w 2048); horizontal pass exact; vertical pass ((h0 >> 4) b0 >> 16) +
+ *     ((h1 >> 4) b1 >> 16), then (v + 2) >> 2.  out == crop sizes: a copy.  |scale - 2| < DBL_EPSILON:
+ *     OpenCV's INTER_AREA fast path, (a + b + c + d + 2) >> 2; a 2 x 2 block cut by the crop's last
+ *     row or column averages the 1 or 2 samples inside, half to even.
+ * Deviations from the reference: an empty mask clears nothing (np.min of nothing raises there); rows
+ * or columns of the resized background beyond H or W are dropped (the reference's paste raises);
+ * a bg_index, crop or factor that does not fit the stack (crop_w > Wb, f <= 0, ...) shows a zero
+ * background; u is expected in [0, 1] (cuts are kept inside [0, 65536]).  Parity with OpenCV itself
+ * is unpinned, as for zp_crop_image.
+ * H, W, Hb, Wb <= 32768; B * H * W < 2^31 - 1024. */
+int zp_mask_bbox(const uint8_t* mask, int B, int H, int W, int* bbox, void* stream);
+int zp_composite(const uint8_t* fg, const uint8_t* mask, const int* bbox, int B, int H, int W, const uint8_t* bgs,
+                 int n_bg, int Hb, int Wb, const int* bg_index, const int* bg_geo, const double* bg_f,
+                 const double* trunc, uint8_t* out, uint8_t* mask_out, void* stream);
+
 /* ---- mesh coder --------------------------------------------------------------------------
  * Surface codes of a raw triangle mesh: per-vertex class id, per-face class id and the class ->
  * 3D-point LUT, replacing the reference's offline tool Generate_Mesh_with_GT_Color (PCL + OpenCV):

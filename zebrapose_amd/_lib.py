@@ -151,6 +151,11 @@ _SIGS = {
     "zp_conv2d_head_ws": (C.c_longlong, [C.POINTER(ConvArgs)]),
     "zp_render_ws_bytes": (i64, [i32, i32, i32, i32, i32]),
     "zp_render": (i32, [i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp, vp, vp, vp]),
+    "zp_render_shaded_ws_bytes": (i64, [i32, i32, i32, i32, i32]),
+    "zp_render_shaded": (i32, [i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp, vp, vp,
+                               vp, vp]),
+    "zp_mask_bbox": (i32, [vp, i32, i32, i32, vp, vp]),
+    "zp_composite": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "zp_mesh_code_ws_bytes": (i64, [i32, i32, i32]),
     "zp_mesh_code": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp]),
     "zp_mesh_code_radix_ws_bytes": (i64, [i32, i32, i32, i32]),

@@ -9,6 +9,11 @@ mesh with a batched HIP rasteriser; its ``color`` / ``mask`` stacks are what ``C
 as ``gt_images`` / ``entire_masks``.  The exact semantics are in include/zp.h (zp_render) and, as
 numpy, in tests/render_ref.py.
 
+``MeshRenderer.render_shaded`` adds the Phong-shaded colour image of a vertex-coloured model
+(``zp_render_shaded``, csrc/zp_shade.hip: the reference's lib/meshrenderer/meshrenderer_phong.py),
+from the same visibility pass; ``vertex_normals`` makes normals for a mesh that carries none, and
+zebrapose_amd/synth.py pastes the renders over backgrounds.
+
 Host helpers: ``read_ply`` (numpy-only reader for the GT-colour meshes) and
 ``modified_gt_for_symmetry`` (the pose choice of the symmetry-aware ``_GT_v2`` labels,
 generate_training_labels_for_BOP_v2.py:90-208).  Dataset walking and PNG writing are out of scope.
@@ -18,6 +23,10 @@ from __future__ import annotations
 import numpy as np
 
 _OUTPUTS = ("color", "depth", "mask", "face")
+_SHADED_OUTPUTS = ("shaded",) + _OUTPUTS
+# the reference's default light, (400, 400, 400) in GL's eye frame (meshrenderer_phong.py:162), in this
+# project's camera frame: realCamera's view matrix is diag(1, 1, -1) [R | t], so eye = (Xc, Yc, -Zc)
+DEFAULT_LIGHT = (400.0, 400.0, -400.0)
 
 
 def face_bgr_from_ids(face_ids):
@@ -35,9 +44,11 @@ class MeshRenderer:
     vertices [nv, 3] (stored as f32), faces int [nf, 3].  Colours: ``face_colors`` u8 [nf, 3] in the
     output's byte order (B, G, R), or ``colors`` u8 [nv, 3] per vertex as a PLY stores them
     (red, green, blue): a face takes its first vertex's colour (the reference's GT meshes duplicate
-    vertices so every face is uniform).  With neither, ``color`` cannot be rendered."""
+    vertices so every face is uniform).  With neither, ``color`` cannot be rendered.  ``render_shaded``
+    needs per-vertex ``colors`` and ``normals`` f32 [nv, 3] (``vertex_normals`` makes them for a mesh
+    that carries none)."""
 
-    def __init__(self, vertices, faces, colors=None, face_colors=None, device="cuda"):
+    def __init__(self, vertices, faces, colors=None, face_colors=None, device="cuda", normals=None):
         import torch
         v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float32).reshape(-1, 3))
         f = np.asarray(faces)
@@ -64,6 +75,13 @@ class MeshRenderer:
         self.vertices = torch.from_numpy(v).to(self.device)
         self.faces = torch.from_numpy(np.ascontiguousarray(f.astype(np.int32))).to(self.device)
         self.face_bgr = None if fb is None else torch.from_numpy(np.ascontiguousarray(fb)).to(self.device)
+        self.vert_rgb = None if colors is None else torch.from_numpy(np.ascontiguousarray(c)).to(self.device)
+        self.normals = None
+        if normals is not None:
+            n = np.asarray(normals)
+            if n.shape != (len(v), 3):
+                raise ValueError("normals must be [nv, 3]")
+            self.normals = torch.from_numpy(np.ascontiguousarray(n.astype(np.float32))).to(self.device)
         self._ws = {}  # stream handle -> workspace
 
     @classmethod
@@ -127,6 +145,77 @@ class MeshRenderer:
                    ws.data_ptr(), st)
         return out
 
+    def render_shaded(self, R, t, K, height, width, light=None, phong=(0.4, 0.8, 0.3), z_near=1e-6,
+                      outputs=("shaded", "mask")):
+        """``render`` plus ``shaded`` u8 [B, H, W, 3]: the Phong-shaded colour image (B, G, R order,
+        background 0) of meshrenderer_phong.py, from the same visibility pass as the other outputs
+        (zp_render_shaded, include/zp.h).  light [3] or [B, 3]: the light's position in camera
+        coordinates (X right, Y down, Z forward), default the reference's; phong [3] or [B, 3] =
+        (ambient, diffuse, specular) weights."""
+        import torch
+        from . import _lib as L
+        outputs = tuple(outputs)
+        if not outputs or any(o not in _SHADED_OUTPUTS for o in outputs):
+            raise ValueError(f"outputs must be a non-empty subset of {_SHADED_OUTPUTS}")
+        if "color" in outputs and self.face_bgr is None:
+            raise ValueError("this mesh has no colours")
+        if "shaded" in outputs and (self.vert_rgb is None or self.normals is None):
+            raise ValueError("shaded needs per-vertex colors and normals")
+        Rn = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(-1, 9))
+        B = len(Rn)
+        tn = np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 3))
+        Kn = np.asarray(K, dtype=np.float64)
+        if Kn.shape == (3, 3):
+            Kn = np.array([Kn[0, 0], Kn[1, 1], Kn[0, 2], Kn[1, 2]])
+        Kn = Kn.reshape(-1, 4)
+        if len(Kn) == 1 and B > 1:
+            Kn = np.repeat(Kn, B, axis=0)
+        Kn = np.ascontiguousarray(Kn)
+        if B == 0 or len(tn) != B or len(Kn) != B:
+            raise ValueError("R, t and K disagree on the batch size")
+        ln = np.asarray(DEFAULT_LIGHT if light is None else light, dtype=np.float64).reshape(-1, 3)
+        pn = np.asarray(phong, dtype=np.float64).reshape(-1, 3)
+        if len(ln) not in (1, B) or len(pn) not in (1, B):
+            raise ValueError("light and phong must be one row or one row per render")
+        lp = np.ascontiguousarray(np.concatenate([np.broadcast_to(ln, (B, 3)), np.broadcast_to(pn, (B, 3))], axis=1))
+        H, W = int(height), int(width)
+        need = L.lib.zp_render_shaded_ws_bytes(B, self.nv, self.nf, H, W)
+        if need < 0:
+            raise ValueError(f"render sizes out of range: B {B}, {H} x {W}")
+        dev = self.device
+        with torch.cuda.device(dev):
+            st = L.stream_ptr(dev)
+            ws = self._ws.get(st)
+            if ws is None or ws.numel() < need:
+                ws = self._ws[st] = torch.empty(need, dtype=torch.uint8, device=dev)
+            pose = torch.from_numpy(np.concatenate([Rn.ravel(), tn.ravel(), Kn.ravel(), lp.ravel()])).to(dev)
+            Rd, td, Kd, ld = pose[:9 * B], pose[9 * B:12 * B], pose[12 * B:16 * B], pose[16 * B:]
+            out = {}
+            for name, shape, dt in (("shaded", (B, H, W, 3), torch.uint8), ("color", (B, H, W, 3), torch.uint8),
+                                    ("depth", (B, H, W), torch.float32), ("mask", (B, H, W), torch.uint8),
+                                    ("face", (B, H, W), torch.int32)):
+                if name in outputs:
+                    out[name] = torch.empty(shape, dtype=dt, device=dev)
+            L.call("zp_render_shaded", B, self.vertices.data_ptr(), L.ptr(self.normals), L.ptr(self.vert_rgb), self.nv,
+                   self.faces.data_ptr(), self.nf, L.ptr(self.face_bgr), Rd.data_ptr(), td.data_ptr(), Kd.data_ptr(),
+                   ld.data_ptr(), H, W, float(z_near), L.ptr(out.get("shaded")), L.ptr(out.get("color")),
+                   L.ptr(out.get("depth")), L.ptr(out.get("mask")), L.ptr(out.get("face")), ws.data_ptr(), st)
+        return out
+
+
+def vertex_normals(vertices, faces):
+    """Area-weighted vertex normals f32 [nv, 3] for a mesh that carries none: each face adds its
+    cross product (v1 - v0) x (v2 - v0) (twice its area along its normal) to its three vertices; the
+    sums are normalised in f64.  A vertex of no face (or of cancelling ones) keeps a zero normal."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    fn = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    n = np.zeros_like(v)
+    for k in range(3):
+        np.add.at(n, f[:, k], fn)
+    ln = np.linalg.norm(n, axis=1, keepdims=True)
+    return np.where(ln > 0, n / np.where(ln > 0, ln, 1.0), 0.0).astype(np.float32)
+
 
 # ---- PLY ---------------------------------------------------------------------------------------
 
@@ -135,11 +224,13 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def read_ply(path):
+def read_ply(path, normals=False):
     """numpy-only reader for a ``models_GT_color/obj_*.ply``: ASCII or binary little-endian; vertex
     x / y / z (f32 or f64), optional u8 red / green / blue, triangular faces as a ``vertex_indices``
     (or ``vertex_index``) list.  Other vertex properties are skipped.  Returns dict(vertices f32
-    [nv, 3], faces i32 [nf, 3], colors u8 [nv, 3] or None).  Anything else raises ValueError."""
+    [nv, 3], faces i32 [nf, 3], colors u8 [nv, 3] or None); with ``normals=True`` also ``normals``
+    f32 [nv, 3] from float or double nx / ny / nz, or None when the file has none.  Anything else
+    raises ValueError."""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.find(b"end_header")
@@ -219,7 +310,16 @@ def read_ply(path):
     colors = None
     if all(rgb):
         colors = np.stack([np.asarray(cols[k]) for k in ("red", "green", "blue")], axis=1).astype(np.uint8)
-    return {"vertices": vertices, "faces": faces.astype(np.int32), "colors": colors}
+    out = {"vertices": vertices, "faces": faces.astype(np.int32), "colors": colors}
+    if normals:
+        nrm = [k in vd for k in ("nx", "ny", "nz")]
+        if any(nrm) and not (all(nrm) and all(vd[k] in ("f4", "f8") for k in ("nx", "ny", "nz"))):
+            raise ValueError(f"{path}: vertex normals must be float or double nx, ny, nz")
+        out["normals"] = None
+        if all(nrm):
+            out["normals"] = np.stack([np.asarray(cols[k], dtype=np.float64) for k in ("nx", "ny", "nz")],
+                                      axis=1).astype(np.float32)
+    return out
 
 
 # ---- symmetry-aware GT pose ------------------------------------------------------------------
