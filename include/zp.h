@@ -48,6 +48,8 @@
  *   zp_mesh_code_radix the same tool run with divide_number_each_itration = 4 / 16 / 256 (the code-radix
  *                      ablation): a balanced d-way split per level, restated (the reference balances
  *                      classes 0 and 1 only)
+ *   zp_mesh_subdivide  step 1 of Binary_Code_GT_Generator/Generate_GT.md (:90-92): Meshlab's 'subdivision
+ *                      surface: mid point' filter, run by hand there until the mesh has > 2^16 vertices
  *   zp_mask_contour    the visible contour handed to the refinement (test.py:300-307: cv2.findContours
  *                      of the entire mask, the visible-mask filter, mapping_pixel_position_to_original_position)
  *   zp_edge_refine_step  one iteration of py_edge_refine (edge_refine/examples/edge_refine.cpp:68-173:
@@ -899,6 +901,46 @@ long long zp_mesh_code_radix_ws_bytes(int nv, int nf, int divide, int levels);
 int zp_mesh_code_radix(const float* verts, int nv, const int* faces, int nf, int divide, int levels, int attempts,
                        int iterations, int grid_log2, long long eps2_q, const uint32_t* draws, int* vertex_ids,
                        int* face_ids, double* lut, void* ws, void* stream);
+
+/* Mesh upsampling: one pass of midpoint subdivision with an edge-length threshold.  Step 1 of the
+ * reference's label-generation recipe (Binary_Code_GT_Generator/Generate_GT.md:90-92) upsamples a model
+ * "until it has more than 2^16 vertices" by hand, with Meshlab's 'subdivision surface: mid point'
+ * filter; zp_mesh_code needs that many vertices too.  The filter is restated with exact semantics
+ * (tests/subdiv_ref.py restates them in numpy; the outputs match it bit for bit and depend on the
+ * order of no summation and of no atomic).  One call is one pass:
+ *   edges:    face (v0, v1, v2) has edge slots 0: (v0, v1), 1: (v1, v2), 2: (v2, v0).  An edge is the
+ *             unordered pair of indices, its key (min << 32) | max; unique edges are taken in ascending
+ *             key order.  An index outside [0, nv) is read as the nearest valid one.
+ *   length:   d = f64(a) - f64(b) per axis (exact), len2 = (dx * dx + dy * dy) + dz * dz, every
+ *             operation rounded once (no FMA).  max_len2 = the maximum over the unique edges; len2 >= 0,
+ *             so any reduction order gives the same bits.
+ *   split:    an edge qualifies iff len2 > abs2 and len2 > rel2 * max_len2 (one IEEE multiply).  If more
+ *             than max_split qualify, only the max_split with the largest len2 split (ties: lower key).
+ *             An edge of length 0 never splits; that covers a face with a repeated index.
+ *   vertices: old vertices keep their indices; the split edges, in ascending key order, get nv, nv + 1,
+ *             ...; position per axis f32((f64(a) + f64(b)) * 0.5): sum and halving are exact, one
+ *             round-to-nearest-even to f32.  parents[i] = (i, i) for i < nv, (min, max) for a new vertex.
+ *   faces:    the children of face i are consecutive, from the exclusive prefix sum of 1 + (number of
+ *             its split edges), orientation kept; mij is the midpoint of edge (vi, vj):
+ *               0 split: (v0, v1, v2)
+ *               3 split: (v0, m01, m20), (m01, v1, m12), (m20, m12, v2), (m01, m12, m20)
+ *               1 split: the face rotated so that the split edge is (v0, v1): (v0, m01, v2), (m01, v1, v2)
+ *               2 split: rotated so that the unsplit edge is (v2, v0): (m01, v1, m12), then the quad
+ *                        (v0, m01, m12, v2) cut by its shorter diagonal: if len2(m01, v2) < len2(v0, m12)
+ *                        strictly (both as above, from the f32 output positions), (v0, m01, v2),
+ *                        (m01, m12, v2); otherwise (v0, m01, m12), (v0, m12, v2).
+ *   counts:   {n_unique_edges, n_split, nv_out, nf_out}.  If nv_out > cap_v or nf_out > cap_f nothing is
+ *             written to out_verts, out_faces and parents; counts and max_len2 are still filled, so the
+ *             caller can size a retry.
+ * verts f32 [nv][3] (finite), faces i32 [nf][3]; outputs out_verts f32 [cap_v][3], out_faces i32
+ * [cap_f][3], parents i32 [cap_v][2], counts i64 [4], max_len2 f64 [1] (device memory, like every
+ * pointer here; the outputs may not overlap the inputs).  1 <= nv <= 2^21, 1 <= nf <= 2^24, abs2 >= 0,
+ * 0 <= rel2 < 1, max_split >= 0, cap_v >= 0, cap_f >= 0; anything else, or a NULL pointer, is ZP_ERR_ARG
+ * before any device call.  ws: zp_mesh_subdivide_ws_bytes bytes (-1: bad sizes). */
+long long zp_mesh_subdivide_ws_bytes(int nv, int nf);
+int zp_mesh_subdivide(const float* verts, int nv, const int* faces, int nf, double abs2, double rel2, int max_split,
+                      float* out_verts, int cap_v, int* out_faces, int cap_f, int* parents, long long* counts,
+                      double* max_len2, void* ws, void* stream);
 
 /* ---- edge refinement -----------------------------------------------------------------------
  * The refine = True branch of the reference's inference (test.py:276-313): the visible contour of the

@@ -160,6 +160,8 @@ _SIGS = {
     "zp_mesh_code": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp]),
     "zp_mesh_code_radix_ws_bytes": (i64, [i32, i32, i32, i32]),
     "zp_mesh_code_radix": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp]),
+    "zp_mesh_subdivide_ws_bytes": (i64, [i32, i32]),
+    "zp_mesh_subdivide": (i32, [vp, i32, vp, i32, f64, f64, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     "zp_mask_contour": (i32, [i32, i32, vp, vp, vp, i32, vp, vp, vp]),
     "zp_edge_refine_ws_bytes": (i64, [i32, i32, i32]),
     "zp_edge_refine_step": (i32, [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, f64, f64, vp, vp, vp, vp, vp, vp, i32,

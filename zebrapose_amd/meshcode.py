@@ -13,6 +13,11 @@ in two (the reference's ``divide_number`` 2); ``encode_mesh_radix`` codes a mesh
 of the code-radix ablation (``divide_number_each_itration`` 4 / 16 / 256) with a balanced d-way split
 per level (zp_mesh_code_radix in include/zp.h, tests/meshcode_radix_ref.py).  Dataset walking and OBJ
 input are out of scope.
+
+The generator's recipe (Binary_Code_GT_Generator/Generate_GT.md, step 1) first upsamples a model past
+2^16 vertices with Meshlab's midpoint-subdivision filter, by hand.  ``upsample_mesh`` /
+``subdivide_midpoint`` do that on the device (``zp_mesh_subdivide``, csrc/zp_subdiv.hip; semantics in
+include/zp.h and, as numpy, in tests/subdiv_ref.py), and ``encode_mesh(..., upsample=True)`` calls it.
 """
 from __future__ import annotations
 
@@ -136,13 +141,131 @@ def _check_mesh(vertices, faces, classes, what):
     return v, np.ascontiguousarray(f.astype(np.int32))
 
 
-def encode_mesh_radix(vertices, faces, divide, levels, attempts=3, iterations=10, eps=1.0, seed=0, device="cuda"):
+_MAX_NV, _MAX_NF, _NO_BUDGET = 1 << 21, 1 << 24, (1 << 31) - 1
+
+
+class UpsampledMesh:
+    """Result of ``subdivide_midpoint`` / ``upsample_mesh``: ``vertices`` f32 [nv, 3] and ``faces`` i32
+    [nf, 3] (numpy, the form ``encode_mesh`` and ``MeshRenderer`` take), ``parents`` i32 [nv, 2] (an
+    input vertex: its own index twice; a new one: the two ends of the edge it halves, indices of this
+    mesh), ``n_input`` (the input's vertex count) and ``pass_sizes`` (the vertex count after each pass)."""
+
+    def __init__(self, vertices, faces, parents, n_input, pass_sizes):
+        self.vertices, self.faces, self.parents = vertices, faces, parents
+        self.n_input, self.pass_sizes = int(n_input), [int(n) for n in pass_sizes]
+
+    def lift(self, attr):
+        """Carry a per-vertex attribute of the input mesh (colours, normals; [n_input, ...]) to this
+        mesh: a new vertex gets the average of its parents', pass by pass, in f64 -> f64 [nv, ...]."""
+        a = np.asarray(attr, dtype=np.float64)
+        if len(a) != self.n_input:
+            raise ValueError(f"attribute has {len(a)} rows, the input mesh had {self.n_input} vertices")
+        prev = self.n_input
+        for n in self.pass_sizes:
+            p = self.parents[prev:n]
+            a = np.concatenate([a, (a[p[:, 0]] + a[p[:, 1]]) * 0.5])
+            prev = n
+        return a
+
+
+class _Subdivider:
+    """The mesh on the device between passes of zp_mesh_subdivide; only ``counts`` comes back per pass."""
+
+    def __init__(self, vertices, faces, device):
+        import torch
+        v, f = _check_mesh(vertices, faces, 1, "1")
+        if len(v) > _MAX_NV or len(f) > _MAX_NF:
+            raise ValueError(f"mesh sizes out of range: {len(v)} vertices, {len(f)} faces")
+        self.dev = torch.device(device)
+        self.host = (v, f)
+        self.n_input, self.pass_sizes = len(v), []
+        with torch.cuda.device(self.dev):
+            self.v, self.f = torch.from_numpy(v).to(self.dev), torch.from_numpy(f).to(self.dev)
+            self.parents = torch.arange(len(v), dtype=torch.int32, device=self.dev).repeat_interleave(2).view(-1, 2)
+
+    def run(self, abs2, rel2, max_split):
+        """One pass -> the number of edges it split."""
+        import torch
+        from . import _lib as L
+        nv, nf = len(self.v), len(self.f)
+        # every split edge adds one vertex, every split edge slot one face
+        cap_v, cap_f = nv + min(int(max_split), 3 * nf), 4 * nf
+        with torch.cuda.device(self.dev):
+            ov = torch.empty((cap_v, 3), dtype=torch.float32, device=self.dev)
+            of = torch.empty((cap_f, 3), dtype=torch.int32, device=self.dev)
+            par = torch.empty((cap_v, 2), dtype=torch.int32, device=self.dev)
+            counts = torch.empty(4, dtype=torch.int64, device=self.dev)
+            mx = torch.empty(1, dtype=torch.float64, device=self.dev)
+            ws = torch.empty(L.lib.zp_mesh_subdivide_ws_bytes(nv, nf), dtype=torch.uint8, device=self.dev)
+            L.call("zp_mesh_subdivide", self.v.data_ptr(), nv, self.f.data_ptr(), nf, float(abs2), float(rel2),
+                   int(max_split), ov.data_ptr(), cap_v, of.data_ptr(), cap_f, par.data_ptr(), counts.data_ptr(),
+                   mx.data_ptr(), ws.data_ptr(), L.stream_ptr(self.dev))
+            _, n_split, nv_out, nf_out = (int(c) for c in counts.cpu())
+            if nv_out > _MAX_NV or nf_out > _MAX_NF:
+                raise ValueError(f"the upsampled mesh is out of range: {nv_out} vertices, {nf_out} faces "
+                                 "(at most 2^21 vertices and 2^24 faces)")
+            par[:nv] = self.parents
+            self.v, self.f, self.parents = ov[:nv_out].clone(), of[:nf_out].clone(), par[:nv_out].clone()
+        self.pass_sizes.append(nv_out)
+        return n_split
+
+    def result(self):
+        if not self.pass_sizes:
+            v, f = self.host
+            return UpsampledMesh(v, f, self.parents.cpu().numpy(), self.n_input, [])
+        return UpsampledMesh(self.v.cpu().numpy(), self.f.cpu().numpy(), self.parents.cpu().numpy(), self.n_input,
+                             self.pass_sizes)
+
+
+def subdivide_midpoint(vertices, faces, iterations=1, threshold=0.0, device="cuda"):
+    """Meshlab's 'subdivision surface: mid point' filter with its two parameters, on the device
+    (zp_mesh_subdivide in include/zp.h; tests/subdiv_ref.py restates it): ``iterations`` passes, each
+    halving every edge longer than ``threshold`` mesh units.  Returns an ``UpsampledMesh``."""
+    iterations, threshold = int(iterations), float(threshold)
+    if iterations < 0:
+        raise ValueError("iterations must be >= 0")
+    if not np.isfinite(threshold) or threshold < 0:
+        raise ValueError("threshold must be finite and >= 0")
+    s = _Subdivider(vertices, faces, device)
+    for _ in range(iterations):
+        s.run(threshold * threshold, 0.0, _NO_BUDGET)
+    return s.result()
+
+
+def upsample_mesh(vertices, faces, min_vertices=65537, max_passes=64, device="cuda"):
+    """Upsample a mesh to exactly ``min_vertices`` vertices (step 1 of the reference's label recipe,
+    Generate_GT.md: "until it has more than 2^16 vertices"): passes of zp_mesh_subdivide that halve the
+    edges longer than half the longest one (rel2 = 0.25, so the long edges of a CAD mesh go first), the
+    longest first and only as many as are still missing.  A mesh that is large enough already comes back
+    unchanged, with no pass.  Raises if a pass splits nothing (every edge has length 0), after
+    ``max_passes`` passes, or past the coder's 2^21 vertices / 2^24 faces.  Returns an ``UpsampledMesh``."""
+    min_vertices, max_passes = int(min_vertices), int(max_passes)
+    if min_vertices > _MAX_NV:
+        raise ValueError(f"min_vertices {min_vertices} is beyond the coder's 2^21 vertices")
+    s = _Subdivider(vertices, faces, device)
+    nv = s.n_input
+    while nv < min_vertices:
+        if len(s.pass_sizes) >= max_passes:
+            raise ValueError(f"{nv} of {min_vertices} vertices after max_passes = {max_passes} passes")
+        if s.run(0.0, 0.25, min_vertices - nv) == 0:
+            raise ValueError("a pass split no edge: every edge of the mesh has length 0")
+        nv = s.pass_sizes[-1]
+    return s.result()
+
+
+def _upsampled(vertices, faces, classes, device):
+    m = upsample_mesh(vertices, faces, min_vertices=classes + 1, device=device)
+    return m.vertices, m.faces
+
+
+def encode_mesh_radix(vertices, faces, divide, levels, attempts=3, iterations=10, eps=1.0, seed=0, device="cuda",
+                      upsample=False):
     """Code a triangle mesh for the d-ary network: ``levels`` levels of the balanced ``divide``-way
     split (d a power of two in 4..256, d^levels <= 65536; zp_mesh_code_radix in include/zp.h), with
     ``attempts`` tries of up to ``iterations`` Lloyd steps per group as in ``encode_mesh``.  vertices
     [nv, 3] (stored as f32, finite, d^levels <= nv <= 2^21), faces int [nf, 3].  The seeds are sampled on
-    the host from ``numpy.random.default_rng(seed)``.  Returns a ``MeshCode`` whose ids fold the digits
-    as ``Decoder(class_base=divide)`` and the GT digit planes do."""
+    the host from ``numpy.random.default_rng(seed)``.  ``upsample`` as in ``encode_mesh``.  Returns a
+    ``MeshCode`` whose ids fold the digits as ``Decoder(class_base=divide)`` and the GT digit planes do."""
     import torch
     from . import _lib as L
     d, levels, attempts, iterations = int(divide), int(levels), int(attempts), int(iterations)
@@ -155,6 +278,8 @@ def encode_mesh_radix(vertices, faces, divide, levels, attempts=3, iterations=10
     if attempts < 1 or iterations < 1:
         raise ValueError("attempts and iterations must be >= 1")
     C = d ** levels
+    if upsample:
+        vertices, faces = _upsampled(vertices, faces, C, device)
     v, f = _check_mesh(vertices, faces, C, f"{d}^{levels}")
     k = grid_log2(v)
     eps2 = eps_to_grid(eps, k)
@@ -176,13 +301,15 @@ def encode_mesh_radix(vertices, faces, divide, levels, attempts=3, iterations=10
     return MeshCode(v, f, (d.bit_length() - 1) * levels, vid, fid, lut, draws, divide=d, levels=levels)
 
 
-def encode_mesh(vertices, faces, bits=16, attempts=3, iterations=10, eps=1.0, seed=0, device="cuda"):
+def encode_mesh(vertices, faces, bits=16, attempts=3, iterations=10, eps=1.0, seed=0, device="cuda", upsample=False):
     """Code a triangle mesh: ``bits`` levels (1..16) of the balanced 2-means split, ``attempts`` tries
     of up to ``iterations`` Lloyd steps per group stopping at a centre shift of ``eps`` mesh units
     (the reference's cv::kmeans(..., TermCriteria(10, 1.0), 3, ...)).  vertices [nv, 3] (stored as
     f32, finite, 2^bits <= nv <= 2^21), faces int [nf, 3].  The seeds are sampled on the host from
     ``numpy.random.default_rng(seed)``; the split runs on the current stream of ``device``.
-    Returns a ``MeshCode``."""
+    ``upsample=True`` first brings a smaller mesh to 2^bits + 1 vertices with ``upsample_mesh`` (the
+    reference's recipe asks for more vertices than classes); the result's ``vertices`` / ``faces`` are
+    then the upsampled ones.  Returns a ``MeshCode``."""
     import torch
     from . import _lib as L
     bits, attempts, iterations = int(bits), int(attempts), int(iterations)
@@ -190,6 +317,8 @@ def encode_mesh(vertices, faces, bits=16, attempts=3, iterations=10, eps=1.0, se
         raise ValueError("bits must be in 1..16")
     if attempts < 1 or iterations < 1:
         raise ValueError("attempts and iterations must be >= 1")
+    if upsample:
+        vertices, faces = _upsampled(vertices, faces, 1 << bits, device)
     v, f = _check_mesh(vertices, faces, 1 << bits, f"2^{bits}")
     k = grid_log2(v)
     eps2 = eps_to_grid(eps, k)
