@@ -307,7 +307,10 @@ int zp_conv2d_wgrad(const zp_wgrad_args* a, void* ws, void* stream);
 /* eval: scale = gamma / sqrt(var + eps); shift = beta + (bias - mean) * scale (bias may be NULL) */
 int zp_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var,
                const float* conv_bias, float eps, int C, float* scale, float* shift, void* stream);
-/* train: merge the [3][parts][C] partial statistics of zp_conv2d(stats) (count = P, checked),
+/* train: merge the [3][parts][C] partial statistics of zp_conv2d(stats); the merged count is the sum
+ * of the parts' own counts (parts of count 0 add nothing).  `count` is the caller's pixel count P: it
+ * must be positive and is NOT compared with that sum (the parts live on the device; a check would
+ * put a synchronisation into the training step).  Then
  * update running stats (momentum, unbiased var; the conv bias, if any, is added to the mean)
  * and emit scale/shift for the apply pass, plus save[4][C] = (mean, invstd, scale, shift) of the
  * raw values (shift = fma(-mean, scale, beta)).
@@ -332,7 +335,8 @@ int zp_bn_bwd_parts(int P, int C);
  * from the raw x exactly as zp_bn_apply formed y (no residual) -- y is not read and may be NULL;
  * partials[0][k][c] = sum g, partials[1][k][c] = sum g*xhat over pixel block k (x == NULL: only sum g);
  * then totals into partials[.][parts][c] and (optional) dgamma = sum g*xhat, dbeta = sum g
- * (written, or added if accumulate). */
+ * (written, or added if accumulate).
+ * C, lddy, cdy0 (and ldy, cy0 for relu 1) are multiples of the 16-byte vector (8 elements, f32: 4): checked. */
 int zp_bn_bwd_reduce(const void* dy, int lddy, int cdy0, const void* y, int ldy, int cy0,
                      const void* x, int P, int C, const float* save, int relu, int dtype,
                      float* partials, float* dgamma, float* dbeta, int accumulate, void* stream);
@@ -344,7 +348,8 @@ int zp_bn_bwd_totals(float* partials, int parts, int C, int out_parts, float* dg
                      int accumulate, void* stream);
 /* dx[p][c] = gamma*invstd*(g - sum_g/P - xhat*sum_gx/P)  (dx dtype, [P][C]); relu as for the
  * reduce (mode 2 needs dx);
- * dres (optional) [p, cdres0+c] = g, or += g if res_accumulate */
+ * dres (optional) [p, cdres0+c] = g, or += g if res_accumulate; alignment as for the reduce, lddres and
+ * cdres0 included (checked) */
 int zp_bn_bwd_apply(const void* dy, int lddy, int cdy0, const void* y, int ldy, int cy0,
                     const void* x, int P, int C, const float* save, const float* partials,
                     const float* gamma, int relu, int dtype, void* dx, void* dres, int lddres,

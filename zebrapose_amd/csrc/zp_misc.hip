@@ -1672,37 +1672,35 @@ extern "C" int zp_bn_train_finalize(float* partials, int parts, int C, long long
   ZP_CHECK_ARG(partials && gamma && beta && running_mean && running_var && scale && shift && save && parts > 0 &&
                    C > 0 && count > 0,
                "zp_bn_train_finalize: bad args");
-  (void)count;
+  // count is only required to be positive: the merged count is the sum of the parts' own counts
+  // (comparing the two would take a device read inside the training step)
   const BnFin f{eps, momentum, gamma, beta, conv_bias, running_mean, running_var, nbt, scale, shift, save};
   hipStream_t st = (hipStream_t)stream;
   // the partials buffer is the caller's scratch (zp_conv2d stats): level 1 merges in place
-  int stride = 1;
   if (parts <= BN_MERGE1_MAX) {  // (both key-15 modes: one level, one launch)
     hipLaunchKernelGGL(k_bn_stat_merge1, dim3((C + 7) / 8), dim3(1024), 0, st, partials, parts, C, f);
     ZP_LAUNCH_CHECK("zp_bn_train_finalize (one level)");
     return ZP_OK;
   }
-  if (parts > 2 * BN_MERGE_R) {
-    const int groups = (C + 31) / 32;
-    static const int env = getenv("ZP_BN_FUSED") ? atoi(getenv("ZP_BN_FUSED")) : 1;
-    const bool fused_on = (g_bn_fused >= 0 ? g_bn_fused : env) != 0;
-    if (fused_on) {
-      unsigned* cnt = (unsigned*)(partials + (size_t)3 * parts * C);
-      if (hipMemsetAsync(cnt, 0, (size_t)groups * sizeof(unsigned), st) != hipSuccess) {
-        set_error("zp_bn_train_finalize: counter reset failed");
-        return ZP_ERR_HIP;
-      }
-      hipLaunchKernelGGL(k_bn_stat_merge_fin, dim3(groups, (parts + BN_MERGE_R - 1) / BN_MERGE_R), dim3(256), 0, st,
-                         partials, parts, C, cnt, f);
-      ZP_LAUNCH_CHECK("zp_bn_train_finalize (fused merge)");
-      return ZP_OK;
+  // more than BN_MERGE1_MAX (> 2 * BN_MERGE_R) parts: always two levels
+  const int groups = (C + 31) / 32;
+  static const int env = getenv("ZP_BN_FUSED") ? atoi(getenv("ZP_BN_FUSED")) : 1;
+  const bool fused_on = (g_bn_fused >= 0 ? g_bn_fused : env) != 0;
+  if (fused_on) {
+    unsigned* cnt = (unsigned*)(partials + (size_t)3 * parts * C);
+    if (hipMemsetAsync(cnt, 0, (size_t)groups * sizeof(unsigned), st) != hipSuccess) {
+      set_error("zp_bn_train_finalize: counter reset failed");
+      return ZP_ERR_HIP;
     }
-    hipLaunchKernelGGL(k_bn_stat_merge, dim3(groups, (parts + BN_MERGE_R - 1) / BN_MERGE_R), dim3(256), 0, st,
-                       partials, parts, C);
-    ZP_LAUNCH_CHECK("zp_bn_train_finalize merge");
-    stride = BN_MERGE_R;
+    hipLaunchKernelGGL(k_bn_stat_merge_fin, dim3(groups, (parts + BN_MERGE_R - 1) / BN_MERGE_R), dim3(256), 0, st,
+                       partials, parts, C, cnt, f);
+    ZP_LAUNCH_CHECK("zp_bn_train_finalize (fused merge)");
+    return ZP_OK;
   }
-  hipLaunchKernelGGL(k_bn_train_finalize, dim3((C + 31) / 32), dim3(256), 0, st, partials, parts, stride, C, f);
+  hipLaunchKernelGGL(k_bn_stat_merge, dim3(groups, (parts + BN_MERGE_R - 1) / BN_MERGE_R), dim3(256), 0, st, partials,
+                     parts, C);
+  ZP_LAUNCH_CHECK("zp_bn_train_finalize merge");
+  hipLaunchKernelGGL(k_bn_train_finalize, dim3(groups), dim3(256), 0, st, partials, parts, BN_MERGE_R, C, f);
   ZP_LAUNCH_CHECK("zp_bn_train_finalize");
   return ZP_OK;
 }
@@ -1763,6 +1761,9 @@ extern "C" int zp_bn_bwd_reduce(const void* dy, int lddy, int cdy0, const void* 
                    (relu != 2 || x) && (!x || save),
                "zp_bn_bwd_reduce: bad args");
   ZP_CHECK_ARG(C / N <= 256 || (C / N) % 256 == 0, "zp_bn_bwd_reduce: C %d", C);
+  // 16-byte loads at dy + p * lddy + cdy0 + c (and at y, where the mask reads it)
+  ZP_CHECK_ARG(lddy % N == 0 && cdy0 % N == 0 && (relu != 1 || (ldy % N == 0 && cy0 % N == 0)),
+               "zp_bn_bwd_reduce: slice alignment");
   const int parts = zp_bn_bwd_parts(P, C);
   const int CV = C / N;
   const int cgroups = CV > 256 ? CV / 256 : 1;
@@ -1816,6 +1817,10 @@ extern "C" int zp_bn_bwd_apply(const void* dy, int lddy, int cdy0, const void* y
                    (!dx || (x && save && partials && gamma)),
                "zp_bn_bwd_apply: bad args");
   ZP_CHECK_ARG(C / N <= 256 || (C / N) % 256 == 0, "zp_bn_bwd_apply: C %d", C);
+  // 16-byte loads / stores at dy, y (where the mask reads it) and dres
+  ZP_CHECK_ARG(lddy % N == 0 && cdy0 % N == 0 && (relu != 1 || (ldy % N == 0 && cy0 % N == 0)) &&
+                   (!dres || (lddres % N == 0 && cdres0 % N == 0)),
+               "zp_bn_bwd_apply: slice alignment");
   const int parts = zp_bn_bwd_parts(P, C);
   const BnTile t = bn_tile(P, C, N);
   const dim3 grid(t.blocks, t.cgroups);
