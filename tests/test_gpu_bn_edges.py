@@ -1,5 +1,5 @@
-"""The train-mode BatchNorm chain of csrc/zp_misc.hip -- zp_bn_train_finalize, zp_bn_apply, zp_bn_bwd_reduce
-(with its totals), zp_bn_bwd_apply -- and the pooled reductions zp_global_avgpool / zp_sum_hw, pinned to
+"""The train-mode BatchNorm chain of csrc/zp_bn.hip -- zp_bn_train_finalize, zp_bn_apply, zp_bn_bwd_reduce
+(with its totals), zp_bn_bwd_apply -- and the pooled reductions zp_global_avgpool / zp_sum_hw (zp_pool.hip), pinned to
 tests/bn_ref.py (numpy f64, stated from include/zp.h) at their edges, straight through the C ABI.
 
 Every buffer lies between two guards; outputs are prefilled with a sentinel, channels of an input outside

@@ -1,4 +1,4 @@
-"""The small kernels between the convolutions (zp_misc.hip), each called through the C ABI and
+"""The small kernels between the convolutions (zp_glue.hip, zp_pool.hip, zp_bn.hip), each called through the C ABI and
 compared with a CPU reference of the same operation on the same stored values: zp_copy_slice,
 zp_head_grad_to_nhwc, zp_add_broadcast_hw, zp_bn_fold, zp_mask_interp / _bwd and zp_threshold.
 
@@ -281,7 +281,7 @@ def test_mask_interp_bwd_refuses_fp16(gpu):
 
 # ------------------------------------------------------------------------------------- zp_threshold
 def _threshold_input(n=777):
-    k = np.float32(8.940696716308594e-08)  # zp_loss.hip / zp_misc.hip kHalf: CPU fp32 sigmoid(x) > 0.5 <=> x > kHalf
+    k = np.float32(8.940696716308594e-08)  # zp_loss.hip / zp_glue.hip kHalf: CPU fp32 sigmoid(x) > 0.5 <=> x > kHalf
     edge = np.array([0.0, -0.0, k, np.nextafter(k, np.float32(1)), np.nextafter(k, np.float32(-1)), np.inf, -np.inf,
                      np.nan, np.float32(1e-45), -np.float32(1e-45)], dtype=np.float32)
     want = np.array([0, 0, 0, 1, 0, 1, 0, 0, 0, 0], dtype=np.float64)

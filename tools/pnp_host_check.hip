@@ -9,7 +9,7 @@
 #include <vector>
 #include "../zebrapose_amd/csrc/zp_pnp.hip"
 namespace zp {
-void set_error(const char*, ...) {}  // the library's error slot lives in zp_misc.hip
+void set_error(const char*, ...) {}  // the library's error slot lives in zp_core.hip
 }
 
 int main(int argc, char** argv) {

@@ -78,7 +78,7 @@ __device__ __forceinline__ uint4 ds_read16(unsigned addr) {
 }
 
 // 2^11 * x for the 8 fp16 values of a fragment (v_pk_mul_f16; exact: fp16 exponent shift, no
-// overflow for |x| < 32 -- the two-plane weight packs flag larger weights, zp_misc.hip)
+// overflow for |x| < 32 -- the two-plane weight packs flag larger weights, zp_pack.hip)
 __device__ __forceinline__ uint4 scale_hi(const uint4 a) {
   typedef _Float16 h2v __attribute__((ext_vector_type(2)));
   const h2v k = {(_Float16)2048.f, (_Float16)2048.f};
