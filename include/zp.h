@@ -60,6 +60,9 @@
  *                      scene_gt_info.json (bbox_visib: bop_dataset_pytorch.py:249, 411; visib_fract:
  *                      tools_for_BOP/bop_io.py:71-72, 269-270), with the visibility test of
  *                      lib/pysixd/visibility.py:29-36 ('bop19' and 'bop18')
+ *   zp_scene_compose   no program of the reference: whole cluttered frames (the BlenderProc 'pbr' frames
+ *                      train_v6.py:138-178 mixes in through second_dataset_ratio) composed from
+ *                      zp_render_shaded's per-instance renders, with exact visible masks
  */
 #ifndef ZP_H_
 #define ZP_H_
@@ -828,6 +831,41 @@ int zp_mask_bbox(const uint8_t* mask, int B, int H, int W, int* bbox, void* stre
 int zp_composite(const uint8_t* fg, const uint8_t* mask, const int* bbox, int B, int H, int W, const uint8_t* bgs,
                  int n_bg, int Hb, int Wb, const int* bg_index, const int* bg_geo, const double* bg_f,
                  const double* trunc, uint8_t* out, uint8_t* mask_out, void* stream);
+
+/* ---- scene compositor -----------------------------------------------------------------------
+ * Whole synthetic scenes from per-instance renders: the colour image, foreground, depth and instance
+ * map of each of n_img images, and every instance's exact visible mask, pixel counts and visible box,
+ * in one pass that reads each depth once.  The reference has no such program (its cluttered training
+ * frames are BlenderProc renders made outside it); tests/scene_ref.py restates the text below in
+ * numpy and every output matches it bit for bit.
+ *   depth f32 [B][H][W]: instance b rendered alone, as zp_render / zp_render_shaded write it; shaded u8
+ *   [B][H][W][3] (B, G, R), needed only for image; img_index i32 [B] (device): the image of instance b,
+ *   in any order.  An instance whose img_index lies outside [0, n_img) belongs to no image, exactly
+ *   as zp_scene_depth ignores it: it is never used as an index, takes part in no image, its mask_visib
+ *   is all 0 and its info is (px_all, 0, 0, 0, -1, -1).  It is not an error.
+ *   winner:  of pixel (i, y, x), among the instances b with img_index[b] == i, by zp_scene_depth's rule:
+ *            a surface is depth > 0 (so 0, a negative value and NaN are none, +inf and a subnormal are
+ *            one), the smallest depth wins, the lowest b on a tie.
+ *   Outputs (each may be NULL): image u8 [n_img][H][W][3] = the winner's shaded pixel, 0 without one
+ *   (needs shaded); fg u8 [n_img][H][W] = 255 with a winner, else 0; scene f32 [n_img][H][W] and
+ *   instance i32 [n_img][H][W] = zp_scene_depth's outputs bit for bit (the winner's depth or 0, the
+ *   winner or -1); mask_visib u8 [B][H][W] = 255 exactly where instance[img_index[b]] == b -- exact
+ *   occupancy, NOT zp_gt_info's delta-tolerance test: it marks precisely the pixels of image that
+ *   show b's colour; info i32 [B][6] = px_all (#depth[b] > 0, the in-frame count), px_visib (#pixels
+ *   won), r1, c1, r2, c2 = the inclusive row / column bounds of mask_visib[b], (0, 0, -1, -1) when
+ *   it is empty, as zp_mask_bbox.
+ *   Every byte of every output asked for is written.  Counters and corners are integers merged with
+ *   integer add / min / max (registers -> wave shuffles -> one atomic per wave), so the output is
+ *   exact, independent of the order of the pixels and bitwise reproducible.  The instances of an
+ *   image are found as zp_scene_depth finds them, by a scan of img_index over all B per workgroup.
+ * 1 <= B, n_img <= 65535 (zp_scene_depth's bound); sizes otherwise as zp_render: H, W <= 32768,
+ * B * H * W and n_img * H * W < 2^31 - 1024.  ws: zp_scene_compose_ws_bytes bytes (-1: bad sizes),
+ * needed only with info.  Bad sizes, a NULL depth or img_index, image without shaded or info without
+ * ws are ZP_ERR_ARG before any device call. */
+long long zp_scene_compose_ws_bytes(int B, int n_img, int H, int W);
+int zp_scene_compose(int B, int n_img, int H, int W, const float* depth, const uint8_t* shaded, const int* img_index,
+                     uint8_t* image, uint8_t* fg, float* scene, int* instance, uint8_t* mask_visib, int* info,
+                     void* ws, void* stream);
 
 /* ---- mesh coder --------------------------------------------------------------------------
  * Surface codes of a raw triangle mesh: per-vertex class id, per-face class id and the class ->

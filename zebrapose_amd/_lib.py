@@ -156,6 +156,8 @@ _SIGS = {
                                vp, vp]),
     "zp_mask_bbox": (i32, [vp, i32, i32, i32, vp, vp]),
     "zp_composite": (i32, [vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "zp_scene_compose_ws_bytes": (i64, [i32, i32, i32, i32]),
+    "zp_scene_compose": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "zp_mesh_code_ws_bytes": (i64, [i32, i32, i32]),
     "zp_mesh_code": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp]),
     "zp_mesh_code_radix_ws_bytes": (i64, [i32, i32, i32, i32]),

@@ -141,16 +141,21 @@ class CropPipeline:
             return np.zeros(4, np.int64), np.zeros(4, np.int64)
         return box, f
 
-    def __call__(self, images, img_index, boxes, gt_images=None, masks=None, entire_masks=None):
+    def __call__(self, images, img_index, boxes, gt_images=None, masks=None, entire_masks=None, gt_index=None):
         """images u8 [N, H, W, 3] (BGR, device); img_index int [B]; boxes = padded boxes int [B, 4].
         Returns dict: x f32 [B, 3, S_img, S_img] and, when the GT inputs are given, code u8
-        [B, L, S_gt, S_gt] (bit planes, or the d-ary digits for class_base d), mask / entire_mask f32 [B, S_gt, S_gt]."""
-        images, gt_images, masks, entire_masks, ii = self._check(images, img_index, gt_images, masks, entire_masks)
+        [B, L, S_gt, S_gt] (bit planes, or the d-ary digits for class_base d), mask / entire_mask f32 [B, S_gt, S_gt].
+        gt_index int [B] (default None: the GT stacks are aligned with the images and crop b reads GT
+        image img_index[b]): the GT stacks have a first dimension Ng of their own, one entry per
+        instance as in a BOP dataset (one GT code image and mask file per instance, one RGB per
+        frame) or in ``synth.SceneBatcher``'s output, and crop b reads GT image gt_index[b]."""
+        images, gt_images, masks, entire_masks, ii, gi = self._check(images, img_index, gt_images, masks, entire_masks,
+                                                                     gt_index)
         bb = torch.as_tensor(np.asarray(boxes), dtype=torch.int32).reshape(len(ii), 4).to(images.device).contiguous()
-        return self._crop(images, ii, bb, gt_images, masks, entire_masks, ii)
+        return self._crop(images, ii, bb, gt_images, masks, entire_masks, gi)
 
     @staticmethod
-    def _check(images, img_index, gt_images, masks, entire_masks):
+    def _check(images, img_index, gt_images, masks, entire_masks, gt_index=None):
         images = _u8(images, "images", 4)
         gt_images = _u8(gt_images, "gt_images", 4)
         masks = _u8(masks, "masks", 3)
@@ -158,13 +163,30 @@ class CropPipeline:
         N, H, W, C = images.shape
         if C != 3:
             raise ValueError("images must be HWC with 3 channels")
-        for t in (gt_images, masks, entire_masks):
-            if t is not None and (t.shape[0] != N or t.shape[1] != H or t.shape[2] != W):
-                raise ValueError("GT images / masks must match the image stack")
+        gts = [t for t in (gt_images, masks, entire_masks) if t is not None]
+        if gt_index is None:
+            Ng = N
+        elif not gts:
+            raise ValueError("gt_index without GT images or masks")
+        else:
+            Ng = gts[0].shape[0]
+        for t in gts:
+            if t.shape[0] != Ng or t.shape[1] != H or t.shape[2] != W:
+                raise ValueError("GT images / masks must match the image stack" if gt_index is None else
+                                 "with gt_index, GT images / masks must agree on their first dimension and match "
+                                 "the images' height and width")
         idx = np.asarray(img_index, dtype=np.int64).reshape(-1)
         if len(idx) == 0 or idx.min() < 0 or idx.max() >= N:
             raise ValueError("img_index out of range")
-        return images, gt_images, masks, entire_masks, torch.from_numpy(idx.astype(np.int32)).to(images.device)
+        ii = torch.from_numpy(idx.astype(np.int32)).to(images.device)
+        if gt_index is None:
+            return images, gt_images, masks, entire_masks, ii, ii
+        g = np.asarray(gt_index.cpu() if isinstance(gt_index, torch.Tensor) else gt_index)
+        if g.ndim != 1 or len(g) != len(idx) or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError(f"gt_index: expected {len(idx)} integers")
+        if g.min() < 0 or g.max() >= Ng:
+            raise ValueError("gt_index out of range")
+        return images, gt_images, masks, entire_masks, ii, torch.from_numpy(g.astype(np.int32)).to(images.device)
 
     def _crop(self, images, ii, bb, gt_images, masks, entire_masks, gt_ii):
         """The two crop kernels: crop b reads images[ii[b]] and the GT stacks' image gt_ii[b]."""
@@ -199,15 +221,16 @@ class CropPipeline:
             fin.append(f)
         return np.stack(aug).astype(np.int32), np.stack(fin).astype(np.int64)
 
-    def train_batch(self, images, img_index, raw_boxes, gt_images, masks, entire_masks, sampler):
+    def train_batch(self, images, img_index, raw_boxes, gt_images, masks, entire_masks, sampler, gt_index=None):
         """The ``is_train`` branch (bop_dataset_pytorch.py:267-277) for a batch: raw_boxes [B, 4] are
         the GT ``bbox_visib`` boxes; ``sampler`` (augment.AugmentSampler) supplies the colour chain's
         draws and, through ``sampler.rng``, aug_Bbox's.  aug boxes -> zp_augment over each crop's
         copied region -> zp_crop_image on the augmented stack -> zp_crop_gt on the untouched GT
         stacks.  Returns ``__call__``'s dict plus ``final_boxes`` (int64 [B, 4], get_final_Bbox) and
-        ``boxes`` (the augmented boxes, int32 [B, 4])."""
+        ``boxes`` (the augmented boxes, int32 [B, 4]).  gt_index as in ``__call__``: per-instance GT stacks."""
         from .augment import augment_images
-        images, gt_images, masks, entire_masks, ii = self._check(images, img_index, gt_images, masks, entire_masks)
+        images, gt_images, masks, entire_masks, ii, gi = self._check(images, img_index, gt_images, masks, entire_masks,
+                                                                     gt_index)
         N, H, W, _ = images.shape
         B = len(ii)
         aug_boxes, final_boxes = self.train_boxes(raw_boxes, W, H, sampler.rng)
@@ -217,6 +240,6 @@ class CropPipeline:
         bb = torch.from_numpy(aug_boxes).to(images.device)
         aug = augment_images(images, ii, batch, bbox=bb, method=self.method)
         out = self._crop(aug, torch.arange(B, dtype=torch.int32, device=images.device), bb, gt_images, masks,
-                         entire_masks, ii)
+                         entire_masks, gi)
         out.update(final_boxes=final_boxes, boxes=aug_boxes, aug=batch)
         return out
