@@ -467,7 +467,8 @@ int zp_threshold(const float* logits, long long n, int out_f64, void* bits, void
  *   (int)(bbox[3]/bbox_size * y + bbox[1]) (truncation toward zero), xyz = lut[id] or 0 if any
  *   component is NaN; counts[b] = number of mask pixels.  ids (optional) = id image [B][H][W].
  *   mask_logits f32 [B][1][H][W], code_logits f32 [B][Lfull][H][W], lut f32 [n_lut][2^L][3],
- *   bbox int32 [B][4], xy int32 [B][H*W][2], xyz f32 [B][H*W][3].
+ *   bbox int32 [B][4], xy int32 [B][H*W][2], xyz f32 [B][H*W][3].  The f64 map is a division, a
+ *   multiply and an add, each rounded on its own (numpy's).  L <= 24, B <= 65535.
  *   ws: zp_decode_ws_bytes(B, H, W) bytes. */
 long long zp_decode_ws_bytes(int B, int H, int W);
 int zp_decode(const float* mask_logits, const float* code_logits, int B, int H, int W, int Lfull,

@@ -1,6 +1,7 @@
 """The unique-correspondence oracle (tests/decode_unique_ref.py) against the reference's own output
-(tests/golden/decode_unique.npz, tools/capture_decode_unique_fixture.py), and the C-ABI's two new
-symbols.  No GPU."""
+(tests/golden/decode_unique.npz, tools/capture_decode_unique_fixture.py), the C-ABI's two new
+symbols, and the host side of the three decode entry points (workspace sizes, the batch limit).  No GPU."""
+import ctypes
 import math
 import os
 import re
@@ -97,3 +98,36 @@ def test_header_and_binding_declare_the_symbols():
     for sym in ("zp_decode_unique_ws_bytes", "zp_decode_unique"):
         assert re.search(r"\b" + sym + r"\s*\(", h), sym
         assert f'"{sym}"' in lib, sym
+
+
+@pytest.mark.parametrize("B,H,W", [(1, 1, 1), (2, 33, 31), (3, 128, 128)])
+def test_workspace_bytes(B, H, W):
+    """the sizes Python allocates from: ids [B][HW], one (unique: two) count per 1024-pixel tile, the
+    unique form's two tables of T = 2^k >= 2 HW slots and three accumulators per pixel; 256 spare bytes"""
+    from zebrapose_amd import _lib as L
+    HW = H * W
+    tiles = (HW + 1023) // 1024
+    T = 2
+    while T < 2 * HW:
+        T *= 2
+    assert L.lib.zp_decode_ws_bytes(B, H, W) == B * HW * 4 + B * tiles * 4 + 256
+    assert L.lib.zp_decode_unique_ws_bytes(B, H, W) == (B * HW * 4 + 2 * B * tiles * 4 + 2 * B * T * 4
+                                                         + 3 * B * HW * 4 + 256)
+
+
+def test_batch_limit():
+    """the grids are (tiles, B): B = 65536 is ZP_ERR_ARG from each entry point (valid pointers and
+    sizes otherwise, never dereferenced: the checks reject before any launch), B = 0 likewise"""
+    from zebrapose_amd import _lib as L
+    p = [ctypes.c_void_p(0x1000 * k) for k in range(1, 12)]
+    m, c, lut, bb, ids, cnt, xy, xyz, ws, mult, mean = p
+    calls = {
+        "zp_decode": lambda B: L.lib.zp_decode(m, c, B, 8, 8, 16, 16, lut, None, bb, 8, ids, cnt, xy, xyz, ws, None),
+        "zp_decode_radix": lambda B: L.lib.zp_decode_radix(m, c, B, 8, 8, 4, 4, lut, None, bb, 8, ids, cnt, xy, xyz, ws,
+                                                           None),
+        "zp_decode_unique": lambda B: L.lib.zp_decode_unique(m, c, B, 8, 8, 16, 16, 2, lut, None, bb, 8, ids, cnt, xy,
+                                                             xyz, mult, mean, ws, None)}
+    for name, f in calls.items():
+        for B in (65536, 0):
+            assert f(B) == 1, (name, B)  # ZP_ERR_ARG (include/zp.h)
+            assert L.lib.zp_last_error() == name.encode() + b": bad sizes"

@@ -281,7 +281,7 @@ def test_mask_interp_bwd_refuses_fp16(gpu):
 
 # ------------------------------------------------------------------------------------- zp_threshold
 def _threshold_input(n=777):
-    k = np.float32(8.940696716308594e-08)  # zp_loss.hip / zp_glue.hip kHalf: CPU fp32 sigmoid(x) > 0.5 <=> x > kHalf
+    k = np.float32(8.940696716308594e-08)  # zp_common.h kHalfLogit: CPU fp32 sigmoid(x) > 0.5 <=> x > kHalfLogit
     edge = np.array([0.0, -0.0, k, np.nextafter(k, np.float32(1)), np.nextafter(k, np.float32(-1)), np.inf, -np.inf,
                      np.nan, np.float32(1e-45), -np.float32(1e-45)], dtype=np.float32)
     want = np.array([0, 0, 0, 1, 0, 1, 0, 0, 0, 0], dtype=np.float64)
@@ -293,7 +293,7 @@ def _threshold_input(n=777):
 
 @pytest.mark.parametrize("out_f64", [0, 1], ids=["u8", "f64"])
 def test_threshold_edges(gpu, out_f64):
-    """bit = x > kHalf at +-0, kHalf and its two neighbours, +-inf, NaN and the smallest subnormals,
+    """bit = x > kHalfLogit at +-0, kHalfLogit and its two neighbours, +-inf, NaN and the smallest subnormals,
     exactly as oracle.ref_cpu.threshold_np; n = 777 ends in a partial block; n = 0 writes nothing."""
     from oracle import ref_cpu
     from zebrapose_amd import _lib as L

@@ -6,7 +6,7 @@ logits, mask_code / use_hist off, and a soft (non-0/1) f64 mask.
 Driven through BinaryCodeLoss / MaskLoss and their autograd functions with (3 * loss_b +
 loss_m).backward(), as the trainer does; references are oracle.ref_cpu (BCE, mask) and
 F.cross_entropy (CE) on the CPU in f64 from the same f32 logits.  The histogram term thresholds the
-f32 sigmoid, as the reference does (x > kHalf); logits are planted at kHalf and its neighbours.
+f32 sigmoid, as the reference does (x > kHalfLogit); logits are planted at kHalfLogit and its neighbours.
 
 Bounds: f64 losses rtol 1e-12, histogram atol 1e-15, code gradients rtol 1e-5 / atol 1e-12, the f32
 mask loss rtol 1e-6 (f64 reduction; the f32 sigmoid and the final cast round), its gradient rtol
@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-KH = np.float32(8.940696716308594e-08)  # zp_loss.hip kHalf: CPU fp32 sigmoid(x) > 0.5  <=>  x > kHalf
+KH = np.float32(8.940696716308594e-08)  # zp_common.h kHalfLogit: CPU fp32 sigmoid(x) > 0.5  <=>  x > kHalfLogit
 PLANT = np.array([40.0, -40.0, 0.0, -0.0, KH, np.nextafter(KH, np.float32(1)), np.nextafter(KH, np.float32(-1))],
                  dtype=np.float32)
 

@@ -16,6 +16,9 @@ namespace zp {
 
 void set_error(const char* fmt, ...);
 
+// the reference thresholds sigmoid(x) > 0.5 on the CPU in fp32 (common_ops.py:5-19)  <=>  x > kHalfLogit
+constexpr float kHalfLogit = 8.940696716308594e-08f;
+
 #define ZP_CHECK_ARG(cond, ...)                 \
   do {                                          \
     if (!(cond)) {                              \

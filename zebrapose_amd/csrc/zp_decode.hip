@@ -2,7 +2,7 @@
 // gather -> row-major compaction of the mask pixels -> original-image coordinates.
 //
 // Reference (lyltc1/ZebraPose):
-//   common_ops.py:5-19                               sigmoid(x) > 0.5 (CPU fp32) == x > 8.940696716308594e-08f
+//   common_ops.py:5-19                               sigmoid(x) > 0.5 (CPU fp32) == x > kHalfLogit
 //   class_id_encoder_decoder.py:17-28                id = sum_i bit_i * 2^(L-1-i)  (channel 0 = MSB)
 //   CNN_output_to_pose.py:53-64                      P2D = (x, y) of mask.nonzero() (row-major),
 //                                                    P3D = LUT[id], NaN rows -> [0,0,0] (kept)
@@ -18,81 +18,39 @@
 // offsets (prefix over the crop's earlier tiles) + block scan + ordered writes.
 #include "zp_common.h"
 
+// the crop -> image map's f64 steps are single IEEE operations (the Makefile passes -ffp-contract=off as well)
+#pragma clang fp contract(off)
+
 namespace zp {
 
 constexpr int DEC_TILE = 1024;  // pixels per tile (256 threads x 4)
-constexpr float kHalfLogit = 8.940696716308594e-08f;
 
-__global__ void __launch_bounds__(256) k_decode_ids(const float* __restrict__ mlog, const float* __restrict__ clog, int HW,
-                                                    int Lfull, int L, int* __restrict__ packed, int* __restrict__ ids,
-                                                    int* __restrict__ tile_cnt, int tiles) {
-  const int b = blockIdx.y, tile = blockIdx.x;
-  const int p0 = tile * DEC_TILE + threadIdx.x * 4;
+// ---- what the tile kernels share ----------------------------------------------------------------
+
+// *dst <- the tile's sum of cnt: xor tree over each wave, four LDS words, thread 0 adds them in order
+__device__ __forceinline__ void tile_count(int cnt, int* __restrict__ dst) {
   __shared__ int wsum[4];
-  int cnt = 0;
-  const float* mrow = mlog + (size_t)b * HW;
-  const float* crow = clog + (size_t)b * Lfull * HW;
-  if (p0 + 3 < HW && (HW & 3) == 0) {
-    float4 m = *(const float4*)(mrow + p0);
-    int id[4] = {0, 0, 0, 0};
-    for (int i = 0; i < L; ++i) {
-      float4 c = *(const float4*)(crow + (size_t)i * HW + p0);
-      id[0] = (id[0] << 1) | (c.x > kHalfLogit);
-      id[1] = (id[1] << 1) | (c.y > kHalfLogit);
-      id[2] = (id[2] << 1) | (c.z > kHalfLogit);
-      id[3] = (id[3] << 1) | (c.w > kHalfLogit);
-    }
-    int mb[4] = {m.x > kHalfLogit, m.y > kHalfLogit, m.z > kHalfLogit, m.w > kHalfLogit};
-    int4 pk = make_int4(mb[0] ? id[0] : -1, mb[1] ? id[1] : -1, mb[2] ? id[2] : -1, mb[3] ? id[3] : -1);
-    *(int4*)(packed + (size_t)b * HW + p0) = pk;
-    if (ids) *(int4*)(ids + (size_t)b * HW + p0) = make_int4(id[0], id[1], id[2], id[3]);
-    cnt = mb[0] + mb[1] + mb[2] + mb[3];
-  } else {
-    for (int k = 0; k < 4; ++k) {
-      int p = p0 + k;
-      if (p >= HW) break;
-      int id = 0;
-      for (int i = 0; i < L; ++i) id = (id << 1) | (crow[(size_t)i * HW + p] > kHalfLogit);
-      int mb = mrow[p] > kHalfLogit;
-      packed[(size_t)b * HW + p] = mb ? id : -1;
-      if (ids) ids[(size_t)b * HW + p] = id;
-      cnt += mb;
-    }
-  }
   for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
   __syncthreads();
-  if (threadIdx.x == 0) tile_cnt[b * tiles + tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  if (threadIdx.x == 0) *dst = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-__global__ void __launch_bounds__(256) k_decode_emit(const int* __restrict__ packed, const int* __restrict__ tile_cnt,
-                                                     int tiles, int H, int W, size_t lut_floats,
-                                                     const float* __restrict__ lut,
-                                                     const int* __restrict__ lut_index, const int* __restrict__ bbox,
-                                                     int bbox_size, int* __restrict__ counts, int* __restrict__ xy,
-                                                     float* __restrict__ xyz) {
-  const int b = blockIdx.y, tile = blockIdx.x;
-  const int HW = H * W;
+// The first output row of a thread that emits `mine` rows: the counts of the crop's earlier tiles
+// (cnt_row[0 .. tile)) plus the tile's exclusive scan.  Thread 0 of tile 0 writes the crop's total.
+__device__ __forceinline__ int tile_emit_pos(const int* __restrict__ cnt_row, int tiles, int tile, int mine,
+                                             int* __restrict__ counts_b) {
   __shared__ int scan[256];
   __shared__ int base_s;
   if (threadIdx.x == 0) {
     int base = 0, total = 0;
     for (int t = 0; t < tiles; ++t) {
-      int c = tile_cnt[b * tiles + t];
+      int c = cnt_row[t];
       if (t < tile) base += c;
       total += c;
     }
     base_s = base;
-    if (tile == 0) counts[b] = total;
-  }
-  const int p0 = tile * DEC_TILE + threadIdx.x * 4;
-  int v[4];
-  int mine = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    int p = p0 + k;
-    v[k] = p < HW ? packed[(size_t)b * HW + p] : -1;
-    mine += v[k] >= 0;
+    if (tile == 0) *counts_b = total;
   }
   scan[threadIdx.x] = mine;
   __syncthreads();
@@ -102,28 +60,27 @@ __global__ void __launch_bounds__(256) k_decode_emit(const int* __restrict__ pac
     scan[threadIdx.x] += t;
     __syncthreads();
   }
-  int pos = base_s + scan[threadIdx.x] - mine;
-  const double bx = bbox[b * 4 + 0], by = bbox[b * 4 + 1];
-  const double rx = (double)bbox[b * 4 + 2] / (double)bbox_size;
-  const double ry = (double)bbox[b * 4 + 3] / (double)bbox_size;
-  const float* L3 = lut + (size_t)(lut_index ? lut_index[b] : 0) * lut_floats;  // (3 floats per class id)
-  int* oxy = xy + (size_t)b * HW * 2;
-  float* oxyz = xyz + (size_t)b * HW * 3;
+  return base_s + scan[threadIdx.x] - mine;
+}
+
+// n <= 4 consecutive floats (vec: all four in one 16-byte load), zeros behind them
+__device__ __forceinline__ void load4(const float* __restrict__ x, int n, bool vec, float* v) {
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (v[k] < 0) continue;
-    int p = p0 + k;
-    int py = p / W, px = p - py * W;
-    // f64 multiply then add, no FMA contraction (numpy order); astype('int') truncates toward zero
-    oxy[2 * pos] = (int)__dadd_rn(__dmul_rn(rx, (double)px), bx);
-    oxy[2 * pos + 1] = (int)__dadd_rn(__dmul_rn(ry, (double)py), by);
-    float a = L3[(size_t)v[k] * 3], c = L3[(size_t)v[k] * 3 + 1], d = L3[(size_t)v[k] * 3 + 2];
-    if (isnan(a) || isnan(c) || isnan(d)) a = c = d = 0.f;
-    oxyz[3 * pos] = a;
-    oxyz[3 * pos + 1] = c;
-    oxyz[3 * pos + 2] = d;
-    ++pos;
+  for (int q = 0; q < 4; ++q) v[q] = 0.f;
+  if (vec) {
+    const float4 t = *(const float4*)x;
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+    for (int q = 0; q < n; ++q) v[q] = x[q];
   }
+}
+
+// bits of one logit plane at four consecutive pixels
+__device__ __forceinline__ void bits4(const float* __restrict__ x, int n, bool vec, int* bit) {
+  float v[4];
+  load4(x, n, vec, v);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) bit[q] = v[q] > kHalfLogit;
 }
 
 // argmax over the d class logits of step i at four consecutive pixels (planes HW apart): the first
@@ -138,20 +95,114 @@ __device__ __forceinline__ void digits4(const float* __restrict__ x, size_t HW, 
     dg[q] = 0;
   }
   for (int k = 0; k < d; ++k) {
-    const float* xr = x + (size_t)k * HW;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (vec) {
-      const float4 t = *(const float4*)xr;
-      v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-      for (int q = 0; q < n; ++q) v[q] = xr[q];
-    }
+    float v[4];
+    load4(x + (size_t)k * HW, n, vec, v);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       if (k == 0 || v[q] > best[q]) {
         best[q] = v[q];
         dg[q] = k;
       }
+  }
+}
+
+// One crop's output rows and its crop -> image map (CNN_output_to_pose.py:34-50).
+struct EmitCrop {
+  double bx, by, rx, ry;
+  const float* L3;  // the crop's LUT (3 floats per class id)
+  int* oxy;
+  float* oxyz;
+  __device__ __forceinline__ EmitCrop(int b, int HW, size_t lut_floats, const float* __restrict__ lut,
+                                      const int* __restrict__ lut_index, const int* __restrict__ bbox, int bbox_size,
+                                      int* __restrict__ xy, float* __restrict__ xyz) {
+    bx = bbox[b * 4 + 0], by = bbox[b * 4 + 1];
+    rx = (double)bbox[b * 4 + 2] / (double)bbox_size;
+    ry = (double)bbox[b * 4 + 3] / (double)bbox_size;
+    L3 = lut + (size_t)(lut_index ? lut_index[b] : 0) * lut_floats;
+    oxy = xy + (size_t)b * HW * 2;
+    oxyz = xyz + (size_t)b * HW * 3;
+  }
+};
+
+// row pos of the crop <- the crop point (x, y) mapped to the image, and the 3D point of class id.
+// x' = int(w / S * x + x0): a multiply, then an add (numpy's order), then astype('int')'s truncation.
+__device__ __forceinline__ void emit_row(const EmitCrop& c, int pos, double x, double y, int id) {
+  const double tx = c.rx * x, ty = c.ry * y;
+  c.oxy[2 * pos] = (int)(tx + c.bx);
+  c.oxy[2 * pos + 1] = (int)(ty + c.by);
+  float p0 = c.L3[(size_t)id * 3], p1 = c.L3[(size_t)id * 3 + 1], p2 = c.L3[(size_t)id * 3 + 2];
+  if (isnan(p0) || isnan(p1) || isnan(p2)) p0 = p1 = p2 = 0.f;
+  c.oxyz[3 * pos] = p0;
+  c.oxyz[3 * pos + 1] = p1;
+  c.oxyz[3 * pos + 2] = p2;
+}
+
+// ---- pass 1: class ids ----------------------------------------------------------------------------
+// packed <- id under the mask, -1 elsewhere; ids (optional) <- id; tile_cnt <- mask pixels per tile.
+// id = sum_i digit_i * d^(L-1-i) (Horner) over the crop's Lfull code planes.  RADIX: step i owns d
+// planes and its digit is their argmax (Lfull = L * d); else d = 2, step i owns one plane and its
+// digit is the plane's bit (the leading L of Lfull planes: ignore_bit).
+template <bool RADIX>
+__global__ void __launch_bounds__(256) k_decode_ids(const float* __restrict__ mlog, const float* __restrict__ clog, int HW,
+                                                    int Lfull, int L, int d, int* __restrict__ packed,
+                                                    int* __restrict__ ids, int* __restrict__ tile_cnt, int tiles) {
+  const int b = blockIdx.y, tile = blockIdx.x;
+  const int p0 = tile * DEC_TILE + threadIdx.x * 4;
+  int cnt = 0;
+  if (p0 < HW) {
+    const int n = min(4, HW - p0);
+    const bool vec = (HW & 3) == 0;  // the same for every thread; n == 4 then
+    const size_t o = (size_t)b * HW + p0;
+    const float* crow = clog + (size_t)b * Lfull * HW + p0;
+    int mb[4], id[4] = {0, 0, 0, 0};
+    bits4(mlog + o, n, vec, mb);
+    for (int i = 0; i < L; ++i) {
+      int dg[4];
+      if constexpr (RADIX) digits4(crow + (size_t)i * d * HW, (size_t)HW, d, n, vec, dg);
+      else bits4(crow + (size_t)i * HW, n, vec, dg);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) id[q] = id[q] * (RADIX ? d : 2) + dg[q];
+    }
+    if (vec) {
+      *(int4*)(packed + o) = make_int4(mb[0] ? id[0] : -1, mb[1] ? id[1] : -1, mb[2] ? id[2] : -1, mb[3] ? id[3] : -1);
+      if (ids) *(int4*)(ids + o) = make_int4(id[0], id[1], id[2], id[3]);
+    } else {
+      for (int q = 0; q < n; ++q) {
+        packed[o + q] = mb[q] ? id[q] : -1;
+        if (ids) ids[o + q] = id[q];
+      }
+    }
+    cnt = mb[0] + mb[1] + mb[2] + mb[3];  // pixels past the crop read as 0
+  }
+  tile_count(cnt, tile_cnt + b * tiles + tile);
+}
+
+// ---- pass 2: one row per mask pixel ---------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_decode_emit(const int* __restrict__ packed, const int* __restrict__ tile_cnt,
+                                                     int tiles, int H, int W, size_t lut_floats,
+                                                     const float* __restrict__ lut,
+                                                     const int* __restrict__ lut_index, const int* __restrict__ bbox,
+                                                     int bbox_size, int* __restrict__ counts, int* __restrict__ xy,
+                                                     float* __restrict__ xyz) {
+  const int b = blockIdx.y, tile = blockIdx.x;
+  const int HW = H * W;
+  const int p0 = tile * DEC_TILE + threadIdx.x * 4;
+  int v[4];
+  int mine = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int p = p0 + k;
+    v[k] = p < HW ? packed[(size_t)b * HW + p] : -1;
+    mine += v[k] >= 0;
+  }
+  int pos = tile_emit_pos(tile_cnt + b * tiles, tiles, tile, mine, counts + b);
+  const EmitCrop c(b, HW, lut_floats, lut, lut_index, bbox, bbox_size, xy, xyz);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (v[k] < 0) continue;
+    int p = p0 + k;
+    int py = p / W, px = p - py * W;
+    emit_row(c, pos++, (double)px, (double)py, v[k]);
   }
 }
 
@@ -171,37 +222,6 @@ __global__ void __launch_bounds__(256) k_code_digits(const float* __restrict__ c
     if (out_f64) ((double*)out)[o + q] = (double)dg[q];
     else ((uint8_t*)out)[o + q] = (uint8_t)dg[q];
   }
-}
-
-// k_decode_ids for d-ary codes: id = sum_i digit_i * d^(L-1-i) (Horner), same packed / ids / tile counts
-__global__ void __launch_bounds__(256) k_decode_ids_radix(const float* __restrict__ mlog, const float* __restrict__ clog,
-                                                          int HW, int L, int d, int* __restrict__ packed,
-                                                          int* __restrict__ ids, int* __restrict__ tile_cnt, int tiles) {
-  const int b = blockIdx.y, tile = blockIdx.x;
-  const int p0 = tile * DEC_TILE + threadIdx.x * 4;
-  __shared__ int wsum[4];
-  int cnt = 0;
-  if (p0 < HW) {
-    const int n = min(4, HW - p0);
-    const bool vec = n == 4 && (HW & 3) == 0;
-    int id[4] = {0, 0, 0, 0};
-    for (int i = 0; i < L; ++i) {
-      int dg[4];
-      digits4(clog + ((size_t)(b * L + i) * d) * HW + p0, (size_t)HW, d, n, vec, dg);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) id[q] = id[q] * d + dg[q];
-    }
-    for (int q = 0; q < n; ++q) {
-      const int mb = mlog[(size_t)b * HW + p0 + q] > kHalfLogit;
-      packed[(size_t)b * HW + p0 + q] = mb ? id[q] : -1;
-      if (ids) ids[(size_t)b * HW + p0 + q] = id[q];
-      cnt += mb;
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) tile_cnt[b * tiles + tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
 // ---- unique correspondences (CNN_output_to_pose.py:67-91): one row per decoded class ----------
@@ -253,7 +273,6 @@ __global__ void __launch_bounds__(256) k_unique_accum(const int* __restrict__ sl
   const int b = blockIdx.y, tile = blockIdx.x;
   const unsigned* fb = first + ((size_t)b << logT);
   const int p0 = tile * DEC_TILE + threadIdx.x * 4;
-  __shared__ int wsum[4];
   int cnt = 0;
   for (int k = 0; k < 4; ++k) {
     const int p = p0 + k;
@@ -269,13 +288,11 @@ __global__ void __launch_bounds__(256) k_unique_accum(const int* __restrict__ sl
     atomicAdd(&acc_y[o], py);
     cnt += f == p;
   }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) head_cnt[b * tiles + tile] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  tile_count(cnt, head_cnt + b * tiles + tile);
 }
 
-// pass 3: k_decode_emit over the heads (a pixel that is its class's first), in row-major order
+// pass 3: k_decode_emit over the heads (a pixel that is its class's first), in row-major order, at
+// the class's mean pixel: exact integer sums, one correctly rounded division per axis
 __global__ void __launch_bounds__(256) k_unique_emit(const int* __restrict__ slots, const int* __restrict__ head_cnt,
                                                      int tiles, int H, int W, int logT, const int* __restrict__ keys,
                                                      const unsigned* __restrict__ first, const int* __restrict__ acc_n,
@@ -285,23 +302,8 @@ __global__ void __launch_bounds__(256) k_unique_emit(const int* __restrict__ slo
                                                      int bbox_size, int* __restrict__ counts, int* __restrict__ xy,
                                                      float* __restrict__ xyz, int* __restrict__ mult,
                                                      double* __restrict__ mean_xy) {
-  // every f64 operation of this kernel is rounded on its own.  The __dmul_rn / __dadd_rn wrappers do
-  // not ensure that: they inline to a plain multiply and add, which the compiler contracts into an FMA.
-#pragma clang fp contract(off)
   const int b = blockIdx.y, tile = blockIdx.x;
   const int HW = H * W;
-  __shared__ int scan[256];
-  __shared__ int base_s;
-  if (threadIdx.x == 0) {
-    int base = 0, total = 0;
-    for (int t = 0; t < tiles; ++t) {
-      int c = head_cnt[b * tiles + t];
-      if (t < tile) base += c;
-      total += c;
-    }
-    base_s = base;
-    if (tile == 0) counts[b] = total;
-  }
   const int* kb = keys + ((size_t)b << logT);
   const unsigned* fb = first + ((size_t)b << logT);
   const int p0 = tile * DEC_TILE + threadIdx.x * 4;
@@ -314,37 +316,16 @@ __global__ void __launch_bounds__(256) k_unique_emit(const int* __restrict__ slo
     v[k] = (s >= 0 && (int)fb[s] == p) ? kb[s] : -1;
     mine += v[k] >= 0;
   }
-  scan[threadIdx.x] = mine;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {
-    int t = threadIdx.x >= off ? scan[threadIdx.x - off] : 0;
-    __syncthreads();
-    scan[threadIdx.x] += t;
-    __syncthreads();
-  }
-  int pos = base_s + scan[threadIdx.x] - mine;
-  const double bx = bbox[b * 4 + 0], by = bbox[b * 4 + 1];
-  const double rx = (double)bbox[b * 4 + 2] / (double)bbox_size;
-  const double ry = (double)bbox[b * 4 + 3] / (double)bbox_size;
-  const float* L3 = lut + (size_t)(lut_index ? lut_index[b] : 0) * lut_floats;
-  int* oxy = xy + (size_t)b * HW * 2;
-  float* oxyz = xyz + (size_t)b * HW * 3;
+  int pos = tile_emit_pos(head_cnt + b * tiles, tiles, tile, mine, counts + b);
+  const EmitCrop c(b, HW, lut_floats, lut, lut_index, bbox, bbox_size, xy, xyz);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     if (v[k] < 0) continue;
     const size_t o = (size_t)b * HW + p0 + k;
     const int n = acc_n[o];
-    // exact integer sums, one correctly rounded division per axis; then multiply, add (no FMA), truncate
     const double mx = (double)acc_x[o] / (double)n;
     const double my = (double)acc_y[o] / (double)n;
-    const double tx = rx * mx, ty = ry * my;
-    oxy[2 * pos] = (int)(tx + bx);
-    oxy[2 * pos + 1] = (int)(ty + by);
-    float a = L3[(size_t)v[k] * 3], c = L3[(size_t)v[k] * 3 + 1], d = L3[(size_t)v[k] * 3 + 2];
-    if (isnan(a) || isnan(c) || isnan(d)) a = c = d = 0.f;
-    oxyz[3 * pos] = a;
-    oxyz[3 * pos + 1] = c;
-    oxyz[3 * pos + 2] = d;
+    emit_row(c, pos, mx, my, v[k]);
     if (mult) mult[(size_t)b * HW + pos] = n;
     if (mean_xy) {
       mean_xy[((size_t)b * HW + pos) * 2] = mx;
@@ -370,31 +351,89 @@ __global__ void k_lut_coarsen(const double* __restrict__ lut, int k, int n_new, 
   out[(size_t)nid * 3 + 2] = (float)(s2 / nch);
 }
 
+// ---- host -----------------------------------------------------------------------------------------
+
+inline int dec_tiles(long long HW) { return (int)((HW + DEC_TILE - 1) / DEC_TILE); }
+
+// Each workspace is laid out by one carve, called with a null base for its size.  Every part is
+// 4-byte words, so the parts follow each other unpadded; 256 spare bytes close the workspace.
+struct DecWs {
+  int* packed;    // [B][HW] id under the mask, -1 elsewhere
+  int* tile_cnt;  // [B][tiles] mask pixels
+};
+
+inline DecWs dec_carve(void* ws, int B, long long HW, long long* total) {
+  DecWs w;
+  w.packed = (int*)ws;
+  w.tile_cnt = w.packed + B * HW;
+  if (total) *total = (w.tile_cnt + (long long)B * dec_tiles(HW) - w.packed) * 4 + 256;
+  return w;
+}
+
+struct UqWs {
+  int* slots;                  // [B][HW] DecWs::packed, then the slot of the id in the crop's table
+  int *tile_cnt, *head_cnt;    // [B][tiles] mask pixels; first pixels of a class
+  int* keys;                   // [B][T] class ids, T = 2^logT >= 2 * HW slots per crop
+  unsigned* first;             // [B][T] first pixels.  k_unique_init fills these two with ones
+  int *acc_n, *acc_x, *acc_y;  // [B][HW] and zeroes these: pixels, sum x, sum y of the class that starts here
+  int logT;
+};
+
+inline UqWs uq_carve(void* ws, int B, long long HW, long long* total) {
+  UqWs w;
+  w.logT = 1;
+  while ((1ll << w.logT) < 2 * HW) ++w.logT;
+  const long long tiles = dec_tiles(HW), T = 1ll << w.logT;
+  w.slots = (int*)ws;
+  w.tile_cnt = w.slots + B * HW;
+  w.head_cnt = w.tile_cnt + B * tiles;
+  w.keys = w.head_cnt + B * tiles;
+  w.first = (unsigned*)(w.keys + B * T);
+  w.acc_n = (int*)(w.first + B * T);
+  w.acc_x = w.acc_n + B * HW;
+  w.acc_y = w.acc_x + B * HW;
+  if (total) *total = (w.acc_y + B * HW - w.slots) * 4 + 256;
+  return w;
+}
+
+// The checks the three decode entry points share (`who`, for the message): pointers, sizes, and
+// *nid <- the d^L class ids of L steps of d classes, at most 2^24.  The grids are (tiles, B): B <= 65535.
+static int dec_check(const char* who, bool pointers, int B, int H, int W, int L, int d, int bbox_size, long long* nid) {
+  ZP_CHECK_ARG(pointers, "%s: null pointer", who);
+  ZP_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && L >= 1 && d >= 2 && d <= 256 && bbox_size > 0, "%s: bad sizes",
+               who);
+  *nid = 1;
+  for (int i = 0; i < L && *nid <= (1ll << 24); ++i) *nid *= d;
+  ZP_CHECK_ARG(*nid <= (1ll << 24), "%s: %d steps of %d classes exceed 2^24 class ids", who, L, d);
+  return ZP_OK;
+}
+
 }  // namespace zp
 
 using namespace zp;
 
 extern "C" long long zp_decode_ws_bytes(int B, int H, int W) {
-  long long HW = (long long)H * W;
-  long long tiles = (HW + DEC_TILE - 1) / DEC_TILE;
-  return (long long)B * HW * 4 + (long long)B * tiles * 4 + 256;
+  long long total;
+  dec_carve(nullptr, B, (long long)H * W, &total);
+  return total;
 }
 
 extern "C" int zp_decode(const float* mask_logits, const float* code_logits, int B, int H, int W, int Lfull, int L,
                          const float* lut, const int* lut_index, const int* bbox, int bbox_size, int* ids, int* counts,
                          int* xy, float* xyz, void* ws, void* stream) {
-  ZP_CHECK_ARG(mask_logits && code_logits && lut && bbox && counts && xy && xyz && ws, "zp_decode: null pointer");
-  ZP_CHECK_ARG(B > 0 && H > 0 && W > 0 && L >= 1 && L <= 24 && L <= Lfull && bbox_size > 0, "zp_decode: bad sizes");
-  const int HW = H * W;
-  const int tiles = (HW + DEC_TILE - 1) / DEC_TILE;
-  int* packed = (int*)ws;
-  int* tile_cnt = packed + (size_t)B * HW;
+  long long nid;
+  if (int rc = dec_check("zp_decode", mask_logits && code_logits && lut && bbox && counts && xy && xyz && ws, B, H, W, L, 2,
+                         bbox_size, &nid))
+    return rc;
+  ZP_CHECK_ARG(L <= Lfull, "zp_decode: %d code channels for %d bits", Lfull, L);
+  const int HW = H * W, tiles = dec_tiles(HW);
+  const DecWs w = dec_carve(ws, B, HW, nullptr);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_decode_ids, dim3(tiles, B), dim3(256), 0, st, mask_logits, code_logits, HW, Lfull, L, packed,
-                     ids, tile_cnt, tiles);
+  hipLaunchKernelGGL(k_decode_ids<false>, dim3(tiles, B), dim3(256), 0, st, mask_logits, code_logits, HW, Lfull, L, 2,
+                     w.packed, ids, w.tile_cnt, tiles);
   ZP_LAUNCH_CHECK("zp_decode ids");
-  hipLaunchKernelGGL(k_decode_emit, dim3(tiles, B), dim3(256), 0, st, packed, tile_cnt, tiles, H, W, (size_t)3 << L, lut,
-                     lut_index, bbox, bbox_size, counts, xy, xyz);
+  hipLaunchKernelGGL(k_decode_emit, dim3(tiles, B), dim3(256), 0, st, w.packed, w.tile_cnt, tiles, H, W, (size_t)3 * nid,
+                     lut, lut_index, bbox, bbox_size, counts, xy, xyz);
   ZP_LAUNCH_CHECK("zp_decode emit");
   return ZP_OK;
 }
@@ -415,86 +454,63 @@ extern "C" int zp_code_digits(const float* code_logits, int B, int L, int d, int
 extern "C" int zp_decode_radix(const float* mask_logits, const float* code_logits, int B, int H, int W, int L, int d,
                                const float* lut, const int* lut_index, const int* bbox, int bbox_size, int* ids,
                                int* counts, int* xy, float* xyz, void* ws, void* stream) {
-  ZP_CHECK_ARG(mask_logits && code_logits && lut && bbox && counts && xy && xyz && ws, "zp_decode_radix: null pointer");
-  ZP_CHECK_ARG(B > 0 && H > 0 && W > 0 && L >= 1 && d >= 2 && d <= 256 && bbox_size > 0, "zp_decode_radix: bad sizes");
-  long long nid = 1;  // d^L class ids, at most 2^24 (zp_decode's limit)
-  for (int i = 0; i < L && nid <= (1ll << 24); ++i) nid *= d;
-  ZP_CHECK_ARG(nid <= (1ll << 24), "zp_decode_radix: %d steps of %d classes exceed 2^24 class ids", L, d);
-  const int HW = H * W;
-  const int tiles = (HW + DEC_TILE - 1) / DEC_TILE;
-  int* packed = (int*)ws;
-  int* tile_cnt = packed + (size_t)B * HW;
+  long long nid;
+  if (int rc = dec_check("zp_decode_radix", mask_logits && code_logits && lut && bbox && counts && xy && xyz && ws, B, H, W,
+                         L, d, bbox_size, &nid))
+    return rc;
+  const int HW = H * W, tiles = dec_tiles(HW);
+  const DecWs w = dec_carve(ws, B, HW, nullptr);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_decode_ids_radix, dim3(tiles, B), dim3(256), 0, st, mask_logits, code_logits, HW, L, d, packed, ids,
-                     tile_cnt, tiles);
+  hipLaunchKernelGGL(k_decode_ids<true>, dim3(tiles, B), dim3(256), 0, st, mask_logits, code_logits, HW, L * d, L, d,
+                     w.packed, ids, w.tile_cnt, tiles);
   ZP_LAUNCH_CHECK("zp_decode_radix ids");
-  hipLaunchKernelGGL(k_decode_emit, dim3(tiles, B), dim3(256), 0, st, packed, tile_cnt, tiles, H, W, (size_t)3 * nid, lut,
-                     lut_index, bbox, bbox_size, counts, xy, xyz);
+  hipLaunchKernelGGL(k_decode_emit, dim3(tiles, B), dim3(256), 0, st, w.packed, w.tile_cnt, tiles, H, W, (size_t)3 * nid,
+                     lut, lut_index, bbox, bbox_size, counts, xy, xyz);
   ZP_LAUNCH_CHECK("zp_decode_radix emit");
   return ZP_OK;
 }
 
-// workspace of zp_decode_unique: slots [B][HW], mask and head tile counts [2][B][tiles], then
-// keys [B][T] and first [B][T] (filled with ones), then n / sum x / sum y [3][B][HW] (zeroed): k_unique_init
-static int uq_log_table(long long HW) {
-  int logT = 1;
-  while ((1ll << logT) < 2 * HW) ++logT;
-  return logT;
-}
-
 extern "C" long long zp_decode_unique_ws_bytes(int B, int H, int W) {
-  long long HW = (long long)H * W;
-  long long tiles = (HW + DEC_TILE - 1) / DEC_TILE;
-  long long T = 1ll << uq_log_table(HW);
-  return (long long)B * HW * 4 + 2 * (long long)B * tiles * 4 + 2 * (long long)B * T * 4 + 3 * (long long)B * HW * 4 + 256;
+  long long total;
+  uq_carve(nullptr, B, (long long)H * W, &total);
+  return total;
 }
 
 extern "C" int zp_decode_unique(const float* mask_logits, const float* code_logits, int B, int H, int W, int Lfull, int L,
                                 int d, const float* lut, const int* lut_index, const int* bbox, int bbox_size, int* ids,
                                 int* counts, int* xy, float* xyz, int* mult, double* mean_xy, void* ws, void* stream) {
-  ZP_CHECK_ARG(mask_logits && code_logits && lut && bbox && counts && xy && xyz && ws, "zp_decode_unique: null pointer");
-  ZP_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && L >= 1 && d >= 2 && d <= 256 && bbox_size > 0,
-               "zp_decode_unique: bad sizes");
-  long long nid = 1;  // class ids: 2^L (d == 2) or d^L, at most 2^24 as in zp_decode / zp_decode_radix
-  for (int i = 0; i < L && nid <= (1ll << 24); ++i) nid *= d;
-  ZP_CHECK_ARG(nid <= (1ll << 24), "zp_decode_unique: %d steps of %d classes exceed 2^24 class ids", L, d);
+  long long nid;  // class ids: 2^L (d == 2) or d^L
+  if (int rc = dec_check("zp_decode_unique", mask_logits && code_logits && lut && bbox && counts && xy && xyz && ws, B, H,
+                         W, L, d, bbox_size, &nid))
+    return rc;
   ZP_CHECK_ARG(d == 2 ? L <= Lfull : Lfull == L * d, "zp_decode_unique: %d code channels for %d steps of %d classes", Lfull,
                L, d);
   // a class may hold every pixel: its coordinate sums stay below HW * max(H, W), kept in int32
   ZP_CHECK_ARG((long long)H * W * (H > W ? H : W) < (1ll << 31),
                "zp_decode_unique: %d x %d crops could overflow the int32 coordinate sums", H, W);
-  const int HW = H * W;
-  const int tiles = (HW + DEC_TILE - 1) / DEC_TILE;
-  const int logT = uq_log_table(HW);
-  const size_t T = (size_t)1 << logT;
-  int* slots = (int*)ws;
-  int* tile_cnt = slots + (size_t)B * HW;
-  int* head_cnt = tile_cnt + (size_t)B * tiles;
-  int* keys = head_cnt + (size_t)B * tiles;
-  unsigned* first = (unsigned*)(keys + (size_t)B * T);
-  int* acc_n = (int*)(first + (size_t)B * T);
-  int* acc_x = acc_n + (size_t)B * HW;
-  int* acc_y = acc_x + (size_t)B * HW;
+  const int HW = H * W, tiles = dec_tiles(HW);
+  const UqWs w = uq_carve(ws, B, HW, nullptr);
   hipStream_t st = (hipStream_t)stream;
-  const size_t n_ones = 2 * (size_t)B * T, n_all = n_ones + 3 * (size_t)B * HW;  // keys, first | n, sum x, sum y
+  const size_t n_ones = (size_t)(w.acc_n - w.keys), n_all = (size_t)(w.acc_y + (size_t)B * HW - w.keys);
   const size_t init_blocks = (n_all + 255) / 256;
-  hipLaunchKernelGGL(k_unique_init, dim3((unsigned)(init_blocks < 4096 ? init_blocks : 4096)), dim3(256), 0, st, keys, n_ones,
-                     n_all);
+  hipLaunchKernelGGL(k_unique_init, dim3((unsigned)(init_blocks < 4096 ? init_blocks : 4096)), dim3(256), 0, st, w.keys,
+                     n_ones, n_all);
   ZP_LAUNCH_CHECK("zp_decode_unique init");
   if (d == 2)
-    hipLaunchKernelGGL(k_decode_ids, dim3(tiles, B), dim3(256), 0, st, mask_logits, code_logits, HW, Lfull, L, slots, ids,
-                       tile_cnt, tiles);
+    hipLaunchKernelGGL(k_decode_ids<false>, dim3(tiles, B), dim3(256), 0, st, mask_logits, code_logits, HW, Lfull, L, d,
+                       w.slots, ids, w.tile_cnt, tiles);
   else
-    hipLaunchKernelGGL(k_decode_ids_radix, dim3(tiles, B), dim3(256), 0, st, mask_logits, code_logits, HW, L, d, slots,
-                       ids, tile_cnt, tiles);
+    hipLaunchKernelGGL(k_decode_ids<true>, dim3(tiles, B), dim3(256), 0, st, mask_logits, code_logits, HW, Lfull, L, d,
+                       w.slots, ids, w.tile_cnt, tiles);
   ZP_LAUNCH_CHECK("zp_decode_unique ids");
-  hipLaunchKernelGGL(k_unique_insert, dim3(tiles, B), dim3(256), 0, st, slots, HW, logT, keys, first);
+  hipLaunchKernelGGL(k_unique_insert, dim3(tiles, B), dim3(256), 0, st, w.slots, HW, w.logT, w.keys, w.first);
   ZP_LAUNCH_CHECK("zp_decode_unique insert");
-  hipLaunchKernelGGL(k_unique_accum, dim3(tiles, B), dim3(256), 0, st, slots, HW, W, logT, first, acc_n, acc_x, acc_y,
-                     head_cnt, tiles);
+  hipLaunchKernelGGL(k_unique_accum, dim3(tiles, B), dim3(256), 0, st, w.slots, HW, W, w.logT, w.first, w.acc_n, w.acc_x,
+                     w.acc_y, w.head_cnt, tiles);
   ZP_LAUNCH_CHECK("zp_decode_unique accum");
-  hipLaunchKernelGGL(k_unique_emit, dim3(tiles, B), dim3(256), 0, st, slots, head_cnt, tiles, H, W, logT, keys, first,
-                     acc_n, acc_x, acc_y, (size_t)3 * nid, lut, lut_index, bbox, bbox_size, counts, xy, xyz, mult, mean_xy);
+  hipLaunchKernelGGL(k_unique_emit, dim3(tiles, B), dim3(256), 0, st, w.slots, w.head_cnt, tiles, H, W, w.logT, w.keys,
+                     w.first, w.acc_n, w.acc_x, w.acc_y, (size_t)3 * nid, lut, lut_index, bbox, bbox_size, counts, xy, xyz,
+                     mult, mean_xy);
   ZP_LAUNCH_CHECK("zp_decode_unique emit");
   return ZP_OK;
 }

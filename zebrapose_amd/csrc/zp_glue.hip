@@ -53,7 +53,7 @@ __global__ void k_head_grad(const float* __restrict__ dmask, const float* __rest
 
 __global__ void k_threshold(const float* __restrict__ x, long n, int f64, void* out) {
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-    bool b = x[e] > 8.940696716308594e-08f;  // NaN -> false
+    bool b = x[e] > kHalfLogit;  // NaN -> false
     if (f64) ((double*)out)[e] = b ? 1.0 : 0.0;
     else ((uint8_t*)out)[e] = b ? 1 : 0;
   }

@@ -14,7 +14,6 @@
 
 namespace zp {
 
-constexpr float kHalf = 8.940696716308594e-08f;  // CPU fp32 sigmoid(x) > 0.5  <=>  x > kHalf
 constexpr int LOSS_MAXL = 32;
 
 __device__ __forceinline__ double bce_logits(double x, double t) {
@@ -36,7 +35,7 @@ __device__ __forceinline__ double mask_value(const double* m01, const float* mlo
     double v = rint(m01[e]);  // round().clamp(0, 1) (HammingLoss :102; half-to-even like torch.round)
     return v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
   }
-  return mlog[e] > kHalf ? 1.0 : 0.0;
+  return mlog[e] > kHalfLogit ? 1.0 : 0.0;
 }
 
 __device__ __forceinline__ double gt_value(const void* gt, int gt_f64, size_t idx) {
@@ -93,7 +92,7 @@ __global__ void __launch_bounds__(256) k_code_partials(const float* __restrict__
         const double graw = gb[k];
         double t2 = rint(graw);
         t2 = t2 < 0.0 ? 0.0 : (t2 > 1.0 ? 1.0 : t2);
-        double bit = z > kHalf ? 1.0 : 0.0;
+        double bit = z > kHalfLogit ? 1.0 : 0.0;
         h = fabs(bit - t2) * m;
         double zz = mask_code ? mraw * (double)z : (double)z;
         c = bce_logits(zz, graw);
@@ -171,7 +170,7 @@ __global__ void k_code_grad(const float* __restrict__ clog, const double* __rest
   const double scale = gs ? gs[0] : 1.0;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < N; e += (long)gridDim.x * blockDim.x) {
     long b = e / HW, p = e - b * HW;
-    const double m = mask_code ? (m01 ? m01[e] : (mlog[e] > kHalf ? 1.0 : 0.0)) : 1.0;
+    const double m = mask_code ? (m01 ? m01[e] : (mlog[e] > kHalfLogit ? 1.0 : 0.0)) : 1.0;
     for (int i = 0; i < L; ++i) {
       size_t idx = ((size_t)b * L + i) * HW + p;
       double z = m * (double)clog[idx];
@@ -226,7 +225,7 @@ __device__ __forceinline__ int ce_target(const void* gt, int gt_f64, size_t idx,
 
 __device__ __forceinline__ double ce_mask(const double* m01, const float* mlog, size_t e, int mask_code) {
   if (!mask_code) return 1.0;
-  return m01 ? m01[e] : (mlog[e] > kHalf ? 1.0 : 0.0);  // :48 multiplies by the raw f64 mask
+  return m01 ? m01[e] : (mlog[e] > kHalfLogit ? 1.0 : 0.0);  // :48 multiplies by the raw f64 mask
 }
 
 // log-sum-exp of z_k = m * x_k over the d planes at x (stride HW): returns max, *lse = log sum exp(z - max)
