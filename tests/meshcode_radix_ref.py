@@ -1,5 +1,5 @@
 """numpy restatement of the d-ary mesh coder (zp_mesh_code_radix, include/zp.h): the executable
-definition the kernels of csrc/zp_meshcode.hip match bit for bit.  All clustering arithmetic is
+definition the kernels of csrc/zp_meshcode_radix.hip match bit for bit.  All clustering arithmetic is
 int64 and exact, vectorised per level over all groups.  A level's groups are laid out as rows of one
 [G, nmax] table (ascending vertex index along a row, padded at the end: a level's group sizes differ
 by little), so that a group's d centres broadcast along its row.  The grid, the face rule, the LUT

@@ -14,28 +14,21 @@
 //   faces    children of face i at the exclusive prefix sum of 1 + (its split edges), by the templates below
 //
 // One thread per edge slot, unique edge or face; nothing is read back.  The sort key packs the pair as
-// (min << 21) | max (indices stay below 2^21), which orders like the 64-bit key.  From rocPRIM
-// (header-only): the stable radix sort that brings equal edges together and, when a budget binds, ranks
-// the qualifying edges by inverted length bits (stable over edges already in key order, so ties go to
-// the lower key), and the integer scans (exact in any order) that number unique edges, new vertices and
-// child faces.  The one atomic is a maximum over the bit patterns of non-negative doubles.
-#include "zp_common.h"
+// (min << 21) | max (indices stay below 2^21), which orders like the 64-bit key.  Through the wrappers
+// of zp_mesh.h (sort_pairs, inclusive_scan, exclusive_scan): the stable radix sort that brings equal
+// edges together and, when a budget binds, ranks the qualifying edges by inverted length bits (stable
+// over edges already in key order, so ties go to the lower key), and the integer scans (exact in any
+// order) that number unique edges, new vertices and child faces.  The one atomic is a maximum over the
+// bit patterns of non-negative doubles.  The size limits, the workspace carver and clamp_index are the
+// mesh coders' (zp_mesh.h).
+#include "zp_mesh.h"
 
 #include <limits.h>
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 // len2 and the midpoints are single IEEE operations (the Makefile passes -ffp-contract=off as well)
 #pragma clang fp contract(off)
 
 namespace zp {
-
-typedef unsigned long long u64;
-
-constexpr int SD_IDX_BITS = 21;  // nv <= 2^21
-constexpr u64 SD_IDX_MASK = (1ull << SD_IDX_BITS) - 1;
-constexpr long long SD_TEMP_FIXED = 16ll << 20, SD_TEMP_PER_ELEM = 32;  // budget for rocPRIM's temporary storage
 
 struct SWs {
   u64* key;        // [E] slot keys; then the selection keys (inverted length bits)
@@ -54,39 +47,29 @@ struct SWs {
   size_t temp_bytes;
 };
 
-inline size_t sd_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline SWs sd_carve(void* ws, int nf, size_t* total) {
-  char* p = (char*)ws;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    char* r = p + o;
-    o = sd_align(o + bytes);
-    return (void*)r;
-  };
+  Carver c(ws);
   const size_t E = 3 * (size_t)nf;
   SWs w;
-  w.key = (u64*)take(E * 8);
-  w.key2 = (u64*)take(E * 8);
-  w.ekey = (u64*)take(E * 8);
-  w.len2 = (double*)take(E * 8);
-  w.iota = (int*)take(E * 4);
-  w.val2 = (int*)take(E * 4);
-  w.flag = (int*)take(E * 4);
-  w.scan = (int*)take(E * 4);
-  w.slot_edge = (int*)take(E * 4);
-  w.fcnt = (int*)take((size_t)nf * 4);
-  w.foff = (int*)take((size_t)nf * 4);
-  w.hdr = (int*)take(256);
-  w.temp_bytes = (size_t)(SD_TEMP_FIXED + SD_TEMP_PER_ELEM * (long long)E);
-  w.temp = take(w.temp_bytes);
-  if (total) *total = o;
+  w.key = c.take<u64>(E);
+  w.key2 = c.take<u64>(E);
+  w.ekey = c.take<u64>(E);
+  w.len2 = c.take<double>(E);
+  w.iota = c.take<int>(E);
+  w.val2 = c.take<int>(E);
+  w.flag = c.take<int>(E);
+  w.scan = c.take<int>(E);
+  w.slot_edge = c.take<int>(E);
+  w.fcnt = c.take<int>(nf);
+  w.foff = c.take<int>(nf);
+  w.hdr = c.take<int>(64);
+  w.temp_bytes = prim_temp_bytes(E);
+  w.temp = c.take<char>(w.temp_bytes);
+  if (total) *total = c.total();
   return w;
 }
 
-static bool sd_sizes_ok(int nv, int nf) { return nv >= 1 && nv <= (1 << SD_IDX_BITS) && nf >= 1 && nf <= (1 << 24); }
-
-__device__ __forceinline__ int sd_clamp(int i, int nv) { return i < 0 ? 0 : (i >= nv ? nv - 1 : i); }
+static bool sd_sizes_ok(int nv, int nf) { return nv >= 1 && mesh_range_ok(nv, nf); }
 
 __device__ __forceinline__ double sd_len2(const float* __restrict__ a, const float* __restrict__ b) {
   const double dx = (double)a[0] - (double)b[0], dy = (double)a[1] - (double)b[1], dz = (double)a[2] - (double)b[2];
@@ -100,8 +83,8 @@ __global__ void __launch_bounds__(256) k_sd_keys(int E, int nv, const int* __res
   const int s = blockIdx.x * 256 + threadIdx.x;
   if (s >= E) return;
   const int f = s / 3, j = s - 3 * f;
-  const int a = sd_clamp(faces[3 * (size_t)f + j], nv), b = sd_clamp(faces[3 * (size_t)f + (j == 2 ? 0 : j + 1)], nv);
-  key[s] = ((u64)(a < b ? a : b) << SD_IDX_BITS) | (u64)(a < b ? b : a);
+  const int a = clamp_index(faces[3 * (size_t)f + j], nv), b = clamp_index(faces[3 * (size_t)f + (j == 2 ? 0 : j + 1)], nv);
+  key[s] = ((u64)(a < b ? a : b) << M_IDX_BITS) | (u64)(a < b ? b : a);
   iota[s] = s;
   if (s == 0) *max_len2 = 0.0;
 }
@@ -134,7 +117,7 @@ __global__ void __launch_bounds__(256) k_sd_len(int E, int nv, const int* __rest
   double l = 0.0;
   if (e < hdr[0]) {
     const u64 k = ekey[e];
-    const int a = sd_clamp((int)(k >> SD_IDX_BITS), nv), b = sd_clamp((int)(k & SD_IDX_MASK), nv);
+    const int a = clamp_index((int)(k >> M_IDX_BITS), nv), b = clamp_index((int)(k & M_IDX_MASK), nv);
     l = sd_len2(verts + 3 * (size_t)a, verts + 3 * (size_t)b);
   }
   if (e < E) len2[e] = l;
@@ -224,7 +207,7 @@ __global__ void __launch_bounds__(256) k_sd_verts(int n, int nv, int E, int cap_
     const long long id = (long long)nv + scan[i] - 1;
     if (id < nv || id >= cap_v) return;
     const u64 k = ekey[i];
-    const int lo = sd_clamp((int)(k >> SD_IDX_BITS), nv), hi = sd_clamp((int)(k & SD_IDX_MASK), nv);
+    const int lo = clamp_index((int)(k >> M_IDX_BITS), nv), hi = clamp_index((int)(k & M_IDX_MASK), nv);
 #pragma unroll
     for (int a = 0; a < 3; ++a)  // the sum of two f32 and its half are exact in f64: one rounding, to f32
       out_verts[3 * (size_t)id + a] = (float)(((double)verts[3 * (size_t)lo + a] + (double)verts[3 * (size_t)hi + a]) * 0.5);
@@ -255,7 +238,7 @@ __global__ void __launch_bounds__(256) k_sd_emit(int nf, int nv, int E, int cap_
   int v[3], m[3], ns = 0, first = -1, unsplit = -1;
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-    v[j] = sd_clamp(faces[3 * (size_t)f + j], nv);
+    v[j] = clamp_index(faces[3 * (size_t)f + j], nv);
     const int e = slot_edge[3 * (size_t)f + j];
     const bool s = (unsigned)e < (unsigned)E && split[e];
     const long long id = s ? (long long)nv + scan[e] - 1 : -1;
@@ -296,25 +279,6 @@ __global__ void __launch_bounds__(256) k_sd_emit(int nf, int nv, int E, int cap_
   }
 }
 
-// rocPRIM calls: the temporary storage each asks for must fit the workspace's share
-#define SD_PRIM(what, call_with)                                                                              \
-  do {                                                                                                        \
-    size_t need = 0;                                                                                          \
-    void* tmp = nullptr;                                                                                      \
-    hipError_t e = call_with;                                                                                 \
-    if (e == hipSuccess && need > w.temp_bytes) {                                                             \
-      set_error("zp_mesh_subdivide: %s needs %zu bytes of temporary storage, the workspace holds %zu", what, \
-                need, w.temp_bytes);                                                                          \
-      return ZP_ERR_HIP;                                                                                      \
-    }                                                                                                         \
-    tmp = w.temp;                                                                                             \
-    if (e == hipSuccess) e = call_with;                                                                       \
-    if (e != hipSuccess) {                                                                                    \
-      set_error("zp_mesh_subdivide: %s failed: %s", what, hipGetErrorString(e));                              \
-      return ZP_ERR_HIP;                                                                                      \
-    }                                                                                                         \
-  } while (0)
-
 }  // namespace zp
 
 using namespace zp;
@@ -344,12 +308,13 @@ extern "C" int zp_mesh_subdivide(const float* verts, int nv, const int* faces, i
 
   hipLaunchKernelGGL(k_sd_keys, dim3(eblocks), dim3(256), 0, st, E, nv, faces, w.key, w.iota, max_len2);
   ZP_LAUNCH_CHECK("zp_mesh_subdivide keys");
-  SD_PRIM("the edge sort", rocprim::radix_sort_pairs(tmp, need, (const u64*)w.key, w.key2, (const int*)w.iota, w.val2,
-                                                     (size_t)E, 0u, (unsigned)(2 * SD_IDX_BITS), st));
+  int rc = sort_pairs(w.key, w.key2, w.iota, w.val2, E, 2 * M_IDX_BITS, w.temp, w.temp_bytes, st,
+                      "zp_mesh_subdivide (edges)");
+  if (rc != ZP_OK) return rc;
   hipLaunchKernelGGL(k_sd_flag, dim3(eblocks), dim3(256), 0, st, E, (const u64*)w.key2, w.flag);
   ZP_LAUNCH_CHECK("zp_mesh_subdivide flags");
-  SD_PRIM("the edge scan", rocprim::inclusive_scan(tmp, need, (const int*)w.flag, w.scan, (size_t)E,
-                                                   rocprim::plus<int>(), st));
+  rc = inclusive_scan(w.flag, w.scan, E, w.temp, w.temp_bytes, st, "zp_mesh_subdivide (edges)");
+  if (rc != ZP_OK) return rc;
   hipLaunchKernelGGL(k_sd_rank, dim3(eblocks), dim3(256), 0, st, E, (const u64*)w.key2, (const int*)w.val2,
                      (const int*)w.flag, (const int*)w.scan, w.slot_edge, w.ekey, w.hdr);
   ZP_LAUNCH_CHECK("zp_mesh_subdivide ranks");
@@ -366,20 +331,20 @@ extern "C" int zp_mesh_subdivide(const float* verts, int nv, const int* faces, i
     hipLaunchKernelGGL(k_sd_sel_keys, dim3(eblocks), dim3(256), 0, st, E, (const int*)w.hdr, (const double*)w.len2,
                        (const double*)max_len2, abs2, rel2, w.key);
     ZP_LAUNCH_CHECK("zp_mesh_subdivide selection keys");
-    SD_PRIM("the length sort", rocprim::radix_sort_pairs(tmp, need, (const u64*)w.key, w.key2, (const int*)w.iota,
-                                                         w.val2, (size_t)E, 0u, 64u, st));
+    rc = sort_pairs(w.key, w.key2, w.iota, w.val2, E, 64, w.temp, w.temp_bytes, st, "zp_mesh_subdivide (lengths)");
+    if (rc != ZP_OK) return rc;
     hipLaunchKernelGGL(k_sd_take, dim3(eblocks), dim3(256), 0, st, E, max_split, (const u64*)w.key2, (const int*)w.val2,
                        split);
     ZP_LAUNCH_CHECK("zp_mesh_subdivide selection");
   }
-  SD_PRIM("the vertex scan", rocprim::inclusive_scan(tmp, need, (const int*)split, w.scan, (size_t)E,
-                                                     rocprim::plus<int>(), st));
+  rc = inclusive_scan(split, w.scan, E, w.temp, w.temp_bytes, st, "zp_mesh_subdivide (new vertices)");
+  if (rc != ZP_OK) return rc;
 
   hipLaunchKernelGGL(k_sd_fcnt, dim3(fblocks), dim3(256), 0, st, nf, E, (const int*)w.slot_edge, (const int*)split,
                      w.fcnt);
   ZP_LAUNCH_CHECK("zp_mesh_subdivide face counts");
-  SD_PRIM("the face scan", rocprim::exclusive_scan(tmp, need, (const int*)w.fcnt, w.foff, 0, (size_t)nf,
-                                                   rocprim::plus<int>(), st));
+  rc = exclusive_scan(w.fcnt, w.foff, nf, w.temp, w.temp_bytes, st, "zp_mesh_subdivide (child faces)");
+  if (rc != ZP_OK) return rc;
   hipLaunchKernelGGL(k_sd_counts, dim3(1), dim3(64), 0, st, nv, nf, E, cap_v, cap_f, (const int*)w.scan,
                      (const int*)w.fcnt, (const int*)w.foff, w.hdr, counts);
   ZP_LAUNCH_CHECK("zp_mesh_subdivide counts");

@@ -1,4 +1,5 @@
-"""Surface codes of a raw mesh on the device (``zp_mesh_code`` / ``zp_mesh_code_radix``, csrc/zp_meshcode.hip).
+"""Surface codes of a raw mesh on the device (``zp_mesh_code``, csrc/zp_meshcode.hip; ``zp_mesh_code_radix``,
+csrc/zp_meshcode_radix.hip).
 
 The reference codes a mesh offline with the C++ tool
 Binary_Code_GT_Generator/Generate_Mesh_with_GT_Color (PCL + OpenCV): a recursive balanced 2-means
@@ -258,6 +259,36 @@ def _upsampled(vertices, faces, classes, device):
     return m.vertices, m.faces
 
 
+def _encode(vertices, faces, classes, what, size_what, draws_per_attempt, c_name, split_args, bits, attempts,
+            iterations, eps, seed, device, upsample, **code_kw):
+    """What both coders do with checked parameters: ``classes`` classes (``what`` in messages), a
+    [attempts, draws_per_attempt] table of draws, and the C entry ``c_name`` / ``c_name``_ws_bytes, which
+    takes ``split_args`` after the mesh sizes.  ``bits`` and ``code_kw`` go to the ``MeshCode``."""
+    import torch
+    from . import _lib as L
+    if upsample:
+        vertices, faces = _upsampled(vertices, faces, classes, device)
+    v, f = _check_mesh(vertices, faces, classes, what)
+    k = grid_log2(v)
+    eps2 = eps_to_grid(eps, k)
+    draws = np.random.default_rng(seed).integers(0, 1 << 32, size=(attempts, draws_per_attempt), dtype=np.uint32)
+    need = getattr(L.lib, c_name + "_ws_bytes")(len(v), len(f), *split_args)
+    if need < 0:
+        raise ValueError(f"mesh sizes out of range: {len(v)} vertices, {len(f)} faces, {size_what}")
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        vd, fd = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
+        dd = torch.from_numpy(draws.view(np.int32)).to(dev)
+        vid = torch.empty(len(v), dtype=torch.int32, device=dev)
+        fid = torch.empty(len(f), dtype=torch.int32, device=dev)
+        lut = torch.empty((classes, 3), dtype=torch.float64, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        L.call(c_name, vd.data_ptr(), len(v), fd.data_ptr(), len(f), *split_args, attempts, iterations, k, eps2,
+               dd.data_ptr(), vid.data_ptr(), fid.data_ptr(), lut.data_ptr(), ws.data_ptr(), L.stream_ptr(dev))
+        # the inputs and the workspace were allocated on this stream: frees are ordered behind the call
+    return MeshCode(v, f, bits, vid, fid, lut, draws, **code_kw)
+
+
 def encode_mesh_radix(vertices, faces, divide, levels, attempts=3, iterations=10, eps=1.0, seed=0, device="cuda",
                       upsample=False):
     """Code a triangle mesh for the d-ary network: ``levels`` levels of the balanced ``divide``-way
@@ -266,8 +297,6 @@ def encode_mesh_radix(vertices, faces, divide, levels, attempts=3, iterations=10
     [nv, 3] (stored as f32, finite, d^levels <= nv <= 2^21), faces int [nf, 3].  The seeds are sampled on
     the host from ``numpy.random.default_rng(seed)``.  ``upsample`` as in ``encode_mesh``.  Returns a
     ``MeshCode`` whose ids fold the digits as ``Decoder(class_base=divide)`` and the GT digit planes do."""
-    import torch
-    from . import _lib as L
     d, levels, attempts, iterations = int(divide), int(levels), int(attempts), int(iterations)
     if d == 2:
         raise ValueError("divide 2 is the binary code: use encode_mesh")
@@ -278,27 +307,9 @@ def encode_mesh_radix(vertices, faces, divide, levels, attempts=3, iterations=10
     if attempts < 1 or iterations < 1:
         raise ValueError("attempts and iterations must be >= 1")
     C = d ** levels
-    if upsample:
-        vertices, faces = _upsampled(vertices, faces, C, device)
-    v, f = _check_mesh(vertices, faces, C, f"{d}^{levels}")
-    k = grid_log2(v)
-    eps2 = eps_to_grid(eps, k)
-    draws = np.random.default_rng(seed).integers(0, 1 << 32, size=(attempts, (C - 1) // (d - 1)), dtype=np.uint32)
-    need = L.lib.zp_mesh_code_radix_ws_bytes(len(v), len(f), d, levels)
-    if need < 0:
-        raise ValueError(f"mesh sizes out of range: {len(v)} vertices, {len(f)} faces, {d}^{levels} classes")
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        vd, fd = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
-        dd = torch.from_numpy(draws.view(np.int32)).to(dev)
-        vid = torch.empty(len(v), dtype=torch.int32, device=dev)
-        fid = torch.empty(len(f), dtype=torch.int32, device=dev)
-        lut = torch.empty((C, 3), dtype=torch.float64, device=dev)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        L.call("zp_mesh_code_radix", vd.data_ptr(), len(v), fd.data_ptr(), len(f), d, levels, attempts, iterations, k,
-               eps2, dd.data_ptr(), vid.data_ptr(), fid.data_ptr(), lut.data_ptr(), ws.data_ptr(), L.stream_ptr(dev))
-        # as in encode_mesh: everything was allocated on this stream, frees are ordered behind the call
-    return MeshCode(v, f, (d.bit_length() - 1) * levels, vid, fid, lut, draws, divide=d, levels=levels)
+    return _encode(vertices, faces, C, f"{d}^{levels}", f"{d}^{levels} classes", (C - 1) // (d - 1),
+                   "zp_mesh_code_radix", (d, levels), (d.bit_length() - 1) * levels, attempts, iterations, eps, seed,
+                   device, upsample, divide=d, levels=levels)
 
 
 def encode_mesh(vertices, faces, bits=16, attempts=3, iterations=10, eps=1.0, seed=0, device="cuda", upsample=False):
@@ -310,31 +321,10 @@ def encode_mesh(vertices, faces, bits=16, attempts=3, iterations=10, eps=1.0, se
     ``upsample=True`` first brings a smaller mesh to 2^bits + 1 vertices with ``upsample_mesh`` (the
     reference's recipe asks for more vertices than classes); the result's ``vertices`` / ``faces`` are
     then the upsampled ones.  Returns a ``MeshCode``."""
-    import torch
-    from . import _lib as L
     bits, attempts, iterations = int(bits), int(attempts), int(iterations)
     if not 1 <= bits <= 16:
         raise ValueError("bits must be in 1..16")
     if attempts < 1 or iterations < 1:
         raise ValueError("attempts and iterations must be >= 1")
-    if upsample:
-        vertices, faces = _upsampled(vertices, faces, 1 << bits, device)
-    v, f = _check_mesh(vertices, faces, 1 << bits, f"2^{bits}")
-    k = grid_log2(v)
-    eps2 = eps_to_grid(eps, k)
-    draws = np.random.default_rng(seed).integers(0, 1 << 32, size=(attempts, (1 << bits) - 1), dtype=np.uint32)
-    need = L.lib.zp_mesh_code_ws_bytes(len(v), len(f), bits)
-    if need < 0:
-        raise ValueError(f"mesh sizes out of range: {len(v)} vertices, {len(f)} faces, {bits} bits")
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        vd, fd = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
-        dd = torch.from_numpy(draws.view(np.int32)).to(dev)
-        vid = torch.empty(len(v), dtype=torch.int32, device=dev)
-        fid = torch.empty(len(f), dtype=torch.int32, device=dev)
-        lut = torch.empty((1 << bits, 3), dtype=torch.float64, device=dev)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        L.call("zp_mesh_code", vd.data_ptr(), len(v), fd.data_ptr(), len(f), bits, attempts, iterations, k, eps2,
-               dd.data_ptr(), vid.data_ptr(), fid.data_ptr(), lut.data_ptr(), ws.data_ptr(), L.stream_ptr(dev))
-        # the inputs and the workspace were allocated on this stream: frees are ordered behind the call
-    return MeshCode(v, f, bits, vid, fid, lut, draws)
+    return _encode(vertices, faces, 1 << bits, f"2^{bits}", f"{bits} bits", (1 << bits) - 1, "zp_mesh_code", (bits,),
+                   bits, attempts, iterations, eps, seed, device, upsample)
