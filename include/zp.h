@@ -94,7 +94,7 @@ extern "C" {
 #define ZP_F32X3 3
 /* fp32 in the two-plane fp16 split form (eval-mode inference), laid out like ZP_F32X3 with TWO
  * planes [2][...] of IEEE fp16: hi = fp16(v), lo = fp16((v - hi) * 2^11), v = hi + lo * 2^-11 to
- * 22 significant bits (|error| <= 2^-23 |v| in fp16's normal range; |v| must stay below 65504).
+ * 22 significant bits (|error| <= 2^-23 |v| for |v| >= 2^-13, 2^-36 below; |v| must stay below 65504).
  * zp_conv2d forms a*b from hi*hi + (hi*lo + lo*hi) * 2^-11 on fp16 MFMAs (the dropped lo*lo term is
  * below 2^-22 |a b|): 3 MFMAs and 2 staged planes per product instead of ZP_F32X3's 6 and 3.
  * Forward (eval) kernels only. */

@@ -4,23 +4,33 @@
 
 namespace zp {
 
+// One element of torch.optim.Adam (_single_tensor_adam), each op rounded as torch's CPU build rounds it
+// (tests/adam_ref.py restates it, pinned to torch bit for bit):
+//   exp_avg.lerp_(grad, w1 = 1 - beta1)     ATen's lerp is one fma on (end - self):
+//                                             w1 <  0.5: fma(w1, g - m, m);  w1 >= 0.5: fma(w1 - 1, g - m, g)
+//   exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = w2 = 1 - beta2)     fma(w2 * g, g, v * b2)
+//   denom = exp_avg_sq.sqrt() / sqrt(bc2) + eps                             three roundings
+//   param.addcdiv_(exp_avg, denom, value = -lr / bc1)                       p + (a * m) / denom, nothing fused
+__device__ __forceinline__ void adam_elem(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                          float* __restrict__ v, long long e, float lr_bc1, float w1, float b2, float w2,
+                                          float bc2_sqrt, float eps) {
+  const float gg = g[e];
+  float mm = m[e];
+  const float d = __fsub_rn(gg, mm);
+  mm = w1 < 0.5f ? fmaf(w1, d, mm) : fmaf(__fsub_rn(w1, 1.f), d, gg);
+  const float vv = fmaf(__fmul_rn(w2, gg), gg, __fmul_rn(v[e], b2));
+  m[e] = mm;
+  v[e] = vv;
+  // sqrtf and / are the correctly rounded IEEE operations, denormals included (__fsqrt_rn is not: it is the
+  // hardware's approximate root); the Makefile builds this file with -ffp-contract=off, so only the fmaf fuse
+  const float denom = __fadd_rn(__fdiv_rn(sqrtf(vv), bc2_sqrt), eps);
+  p[e] = __fadd_rn(p[e], __fdiv_rn(__fmul_rn(-lr_bc1, mm), denom));
+}
+
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                        long n, float lr_bc1, float w1, float b2, float w2, float bc2_sqrt, float eps) {
-  // torch.optim.Adam (_single_tensor_adam) op by op, each op rounded separately (no FMA contraction):
-  //   exp_avg.lerp_(grad, w1 = 1 - beta1)      (w1 < 0.5: m + w1 * (g - m))
-  //   exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=w2 = 1 - beta2)
-  //   denom = exp_avg_sq.sqrt() / sqrt(bc2) + eps;  param.addcdiv_(exp_avg, denom, value=-lr/bc1)
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
-    const float gg = g[e];
-    float mm = m[e];
-    mm = fmaf(w1, __fsub_rn(gg, mm), mm);  // ATen lerp: fmadd(weight, end - self, self)
-    float vv = __fmul_rn(v[e], b2);
-    vv = __fadd_rn(vv, __fmul_rn(__fmul_rn(w2, gg), gg));
-    m[e] = mm;
-    v[e] = vv;
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(vv), bc2_sqrt), eps);
-    p[e] = __fadd_rn(p[e], __fmul_rn(-lr_bc1, __fdiv_rn(mm, denom)));
-  }
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x)
+    adam_elem(p, g, m, v, e, lr_bc1, w1, b2, w2, bc2_sqrt, eps);
 }
 
 // multi-tensor Adam: one launch updates up to ADAM_MT tensors; the tensor of a block comes from
@@ -61,18 +71,8 @@ __global__ void __launch_bounds__(256) k_adam_multi(const AdamTable T, float lr_
   const float* __restrict__ g = T.g[t];
   float* __restrict__ m = T.m[t];
   float* __restrict__ v = T.v[t];
-  for (long long e = e0 + threadIdx.x; e < e1; e += 256) {
-    // identical op sequence to k_adam (torch.optim.Adam single-tensor order)
-    const float gg = g[e];
-    float mm = m[e];
-    mm = fmaf(w1, __fsub_rn(gg, mm), mm);
-    float vv = __fmul_rn(v[e], b2);
-    vv = __fadd_rn(vv, __fmul_rn(__fmul_rn(w2, gg), gg));
-    m[e] = mm;
-    v[e] = vv;
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(vv), bc2_sqrt), eps);
-    p[e] = __fadd_rn(p[e], __fmul_rn(-lr_bc1, __fdiv_rn(mm, denom)));
-  }
+  for (long long e = e0 + threadIdx.x; e < e1; e += 256)  // the op sequence of k_adam
+    adam_elem(p, g, m, v, e, lr_bc1, w1, b2, w2, bc2_sqrt, eps);
 }
 
 }  // namespace zp

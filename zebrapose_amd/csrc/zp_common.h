@@ -62,7 +62,7 @@ __device__ __forceinline__ float join3(bf16_t h, bf16_t m, bf16_t l) { return (b
 //   SplitF32<3>: bf16 hi + mid + lo, exact (split3 / join3);
 //   SplitF32<2>: IEEE fp16 hi + lo' with v ~ hi + lo' * 2^-11: hi = RNE(v), lo' = RNE((v - hi) * 2^11)
 //     (the residual is scaled into fp16's normal range; 22 significant bits, |v - join| <= 2^-23 |v|
-//     for |v| in fp16's normal range, 2^-36 absolute below it).  Finite |v| >= 65520 rounds hi to
+//     for |v| >= 2^-13, 2^-36 absolute below: there lo' is an fp16 denormal).  Finite |v| >= 65520 rounds hi to
 //     infinity: every store site raises the range flag for it (h2_overflow below) and the engine
 //     re-runs the forward on the full-range SplitF32<3>; non-finite values keep lo' = 0.
 // CS: the factor the lo-plane products carry (k_conv3 scales its correction accumulator by it).

@@ -264,7 +264,8 @@ __global__ void __launch_bounds__(256) k_avgpool_split8(const unsigned short* __
 
 // Window (oy, ox) of the 3x3 / stride-2 / pad-1 pool: per channel, the tap (ky*3+kx, -1 when the
 // window lies outside the output) of its first maximum in (ky, kx) scan order (PyTorch CPU rule:
-// `>` or NaN) and the window's dy.
+// `>` or NaN, the index starting at the window's first in-bounds tap, so a window of -inf alone sends
+// its gradient there) and the window's dy.
 template <typename T>
 __device__ __forceinline__ void mp_window(const T* __restrict__ x, int ldx, int cx0, const T* __restrict__ dy,
                                           int lddy, int cdy0, int b, int c, int IH, int IW, int OH, int OW, int oy,
@@ -288,7 +289,7 @@ __device__ __forceinline__ void mp_window(const T* __restrict__ x, int ldx, int 
       V16<T>::load(x + (((size_t)b * IH + yy) * IW + xx) * ldx + cx0 + c, v);
 #pragma unroll
       for (int i = 0; i < N; ++i)
-        if (v[i] > m[i] || isnan(v[i])) {
+        if (v[i] > m[i] || isnan(v[i]) || pos[i] < 0) {
           m[i] = v[i];
           pos[i] = ky * 3 + kx;
         }
