@@ -1857,7 +1857,7 @@ static int g_quad_min_blocks = 256;    // key 6: fewest workgroups k_conv_quad r
 
 // conv schedule switches: bit 1 XCD-aware tile order, bit 2 s_setprio(1) around the MFMA
 // cluster, bit 3 ping-pong (staggered wave groups), bit 4 tap-row trimming (tap rows that read only
-// padding for a whole tile are skipped), bit 5 spread strip DMA (k_conv_strip only; slower), bit 6
+// padding for a whole tile are skipped; k_conv and the split-fp32 k_conv3), bit 5 spread strip DMA (k_conv_strip only; slower), bit 6
 // k_conv_strip2 instead of k_conv_strip, bit 7 k_conv_quad for the four phases of stride-2 transposed
 // structures (ConvTranspose2d forward, stride-2 conv data gradient), bit 8 k_conv_strip2 issues the
 // next strip's DMA between the MFMAs of a group's first step (DM 2).  Default (measured, profiles/r01_conv_sweep.md,
