@@ -517,6 +517,63 @@ int zp_pnp_ransac(int B, int HW, const int* counts, const int* xy, const float* 
                   int iters, double reproj_err, double confidence, double* R, double* T, int* success,
                   int* inliers, void* ws, void* stream);
 
+/* ---- PnP local optimisation -----------------------------------------------------------------
+ * The reference's default solver is Progressive-X (binary_code_helper/CNN_output_to_pose.py:132-144),
+ * a locally optimised RANSAC; zp_pnp_ransac is its fallback, which ends with one algebraic EPnP fit over
+ * the inliers of the best minimal-sample pose.  zp_pnp_lo adds what a local optimisation adds to that:
+ * the consensus set is re-selected from the fitted pose, and the pose becomes the least-squares minimiser
+ * of the reprojection error over that set.  It does not restate Progressive-X: no graph cuts, no spatial
+ * coherence term, no multi-model proposals; parity with pyprogressivex is not pinned.  The semantics
+ * are restated, in numpy, in tests/pnp_lo_ref.py.
+ *
+ * counts, xy, xyz, K as for zp_pnp_ransac; pose b uses its first n = min(counts[b], HW) rows (a negative
+ * count is 0) and rows past that are never read.  R f64 [B][9] row-major, t f64 [B][3]: zp_pnp_ransac's
+ * outputs.  active i32 [B] or NULL: 0 skips the crop.  One workgroup per crop, the whole loop in one
+ * launch, no host synchronisation, no atomics; all real arithmetic is f64, each step below one IEEE
+ * operation (no fused multiply-add), every sum over a fixed partition and a fixed tree: two runs give
+ * the same bits, and a crop's result does not depend on its place in the batch or on its neighbours.
+ *   projection: p = f64(xyz), (u, v) = f64(xy);
+ *               X = ((R00 p.x + R01 p.y) + R02 p.z) + t.x, likewise Y and Z;
+ *               e.x = u - ((fx X) / Z + cx), e.y = v - ((fy Y) / Z + cy);  r2 = e.x e.x + e.y e.y.
+ *   selection:  S = { i < n : Z > 0, r2 finite and r2 <= thr2 }, thr2 = reproj_err reproj_err, in f64.
+ *               zp_pnp_ransac tests in f32 (its projection stored as f32, thr2 an f32), so the two
+ *               counts may differ by points on the threshold.  The membership mask lives in ws.
+ *   rounds:     for r = 0 .. rounds - 1: select S_r under the current pose; stop if |S_r| < 6 (at r = 0:
+ *               status 2); stop if r > 0 and S_r = S_(r-1) as sets (masks compared exactly); else run
+ *               Levenberg-Marquardt on S_r.
+ *   LM:         lambda = 1e-3.  At most `steps` iterations, each: with a = fx / Z, b = fy / Z,
+ *               c = -((fx X) / (Z Z)), d = -((fy Y) / (Z Z)) the rows of J = Jp [-[Xc]x | I] are
+ *               J0 = (c Y, a Z - c X, -(a Y), a, 0, c), J1 = (d Y - b Z, -(d X), b X, 0, b, d);
+ *               H = sum_S (J0 J0^T + J1 J1^T), each entry's term J0r J0c + J1r J1c; g = sum_S (J0 e.x +
+ *               J1 e.y); C = sum_S r2.  Solve (H + lambda diag(H)) theta = g by Cholesky (column by
+ *               column; a pivot that is not positive and finite is a rejection, never an error).
+ *               Trial pose: E = exp([theta_r]x) by Rodrigues (the series below |theta_r| = 1e-8, as
+ *               zp_edge_refine_step), R' = E R, t' = E t + theta_t.  C' = sum of r2 under the trial pose
+ *               over the same S, +infinity if a point of S has Z <= 0 there.  Accepted iff the
+ *               factorisation succeeded, C' is finite and C' < C: the pose is replaced, lambda =
+ *               max(0.1 lambda, 1e-9), and LM ends if C - C' <= 1e-10 C.  Rejected: lambda = 10 lambda,
+ *               and LM ends if lambda > 1e6 (H, g and C are unchanged and not summed again).
+ *   monotone:   the truncated cost M(pose) = sum_(i<n) min(r2_i, thr2), a point that fails the inlier
+ *               test counting thr2, never rises: selection does not change M, and an accepted step
+ *               lowers sum_S r2 with S fixed and every point of S still in front of the camera, so it
+ *               lowers M.  M(R_out, t_out) <= M(R, t) up to the rounding of the sums.
+ *   outputs:    R_out, t_out: the final pose.  inliers i32 [B]: the size of the set selected under it;
+ *               cost f64 [B]: sum of r2 over that set.
+ *   status i32 [B]: 0 refined; 1 skipped (active[b] = 0, n < 6, or a non-finite entry in R or t);
+ *               2 fewer than 6 inliers under the input pose.  With 1 and 2 the pose is copied through
+ *               bit for bit, cost is 0 and inliers is the count under the input pose (0 with status 1).
+ *   Optional outputs (NULL: not written): trace i32 [B][rounds][2] = (|S_r|, LM iterations run; 0 for a
+ *   round that stopped after its selection), (-1, -1) for rounds not started (all of them with status
+ *   1); Hb f64 [B][28]: for the first LM iteration of round 0 the upper triangle of H by rows (21
+ *   values), then g (6), then C; zeros with status 1 and 2.
+ *   1 <= rounds, steps <= 64; reproj_err > 0 and finite; 1 <= B <= 65535; 1 <= HW <= 2^24; R_out / t_out
+ *   must not be R / t; anything else, or a NULL pointer that is not optional, is ZP_ERR_ARG before any
+ *   device call.  ws: zp_pnp_lo_ws_bytes bytes (-1: bad sizes). */
+long long zp_pnp_lo_ws_bytes(int B, int HW);
+int zp_pnp_lo(int B, int HW, const int* counts, const int* xy, const float* xyz, const double* K, const double* R,
+              const double* t, const int* active, double reproj_err, int rounds, int steps, double* R_out,
+              double* t_out, int* inliers, double* cost, int* status, int* trace, double* Hb, void* ws, void* stream);
+
 /* ---- pose error ----------------------------------------------------
  * ADD / ADI of B pose pairs over one model's points pts f32 [n][3], replacing
  * metric.py:8-18 (bop_toolkit pose_error.add / adi; lib/pysixd/pose_error.py:297-336).

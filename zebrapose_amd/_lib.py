@@ -127,6 +127,8 @@ _SIGS = {
     "zp_conv_tuning": (i32, [i32, i32]),
     "zp_pnp_ws_bytes": (i64, [i32, i32]),
     "zp_pnp_ransac": (i32, [i32, i32, vp, vp, vp, vp, i32, f64, f64, vp, vp, vp, vp, vp, vp]),
+    "zp_pnp_lo_ws_bytes": (i64, [i32, i32]),
+    "zp_pnp_lo": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, f64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "zp_pose_error_ws_bytes": (i64, [i32, i32, i32]),
     "zp_pose_error": (i32, [i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
     "zp_pose_error_sym_ws_bytes": (i64, [i32, i32, i32, i32]),

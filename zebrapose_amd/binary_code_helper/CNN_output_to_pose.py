@@ -142,10 +142,13 @@ def decode_correspondences(mask_image, class_code_image, Bbox, Bbox_Size, dict_c
 
 
 def CNN_outputs_to_object_pose(mask_image, class_code_image, Bbox, Bbox_Size, class_base=2,
-                               dict_class_id_3D_points=None, intrinsic_matrix=None, unique=False):
+                               dict_class_id_3D_points=None, intrinsic_matrix=None, unique=False,
+                               local_optimisation=False):
     """:100-160 -- correspondences on the device, then RANSAC-EPnP (cv2) / Progressive-X as in the
     reference.  Returns (R, t, success).  unique: the reference's other correspondence builder
-    (:67-91, the switch at :114); success then needs 6 distinct class ids."""
+    (:67-91, the switch at :114); success then needs 6 distinct class ids.  local_optimisation: refine
+    the device branch's RANSAC-EPnP pose with zp_pnp_lo (``PnP(local_optimisation=True)``); the
+    pyprogressivex branch does its own and ignores it."""
     if intrinsic_matrix is None:
         intrinsic_matrix = np.zeros((3, 3))
         intrinsic_matrix[0, 0] = 572.4114
@@ -174,15 +177,15 @@ def CNN_outputs_to_object_pose(mask_image, class_code_image, Bbox, Bbox_Size, cl
         else:
             # the reference's default, cv2.solvePnPRansac(EPNP, 2 px, 150 iterations) + Rodrigues
             # (:152-158), runs on the device: zp_pnp_ransac (csrc/zp_pnp.hip)
-            rot, tvecs = _device_pnp(p2d, p3d, intrinsic_matrix)
+            rot, tvecs = _device_pnp(p2d, p3d, intrinsic_matrix, local_optimisation=local_optimisation)
     return rot, tvecs, success
 
 
-def _device_pnp(p2d, p3d, intrinsic_matrix, device="cuda"):
+def _device_pnp(p2d, p3d, intrinsic_matrix, device="cuda", local_optimisation=False):
     from ..pnp import PnP
     n = len(p2d)
     counts = torch.tensor([n], dtype=torch.int32, device=device)
     xy = torch.from_numpy(np.ascontiguousarray(p2d.astype(np.int32))[None]).to(device)
     xyz = torch.from_numpy(np.ascontiguousarray(p3d.astype(np.float32))[None]).to(device)
-    R, t, _, _ = PnP()(counts, xy, xyz, np.asarray(intrinsic_matrix, dtype=np.float64))
+    R, t, _, _ = PnP(local_optimisation=local_optimisation)(counts, xy, xyz, np.asarray(intrinsic_matrix, dtype=np.float64))
     return R[0].cpu().numpy(), t[0].cpu().numpy().reshape(3, 1)
